@@ -13,10 +13,17 @@ Multi-GPU: every rank runs its own independent chain (its own prompt/noise), exa
 `index = (step-1)*world_size + rank` sharding — no collective inside the loop ("scaling": "weak");
 value = total steps of all ranks / max-over-ranks time.
 
+A plain run sets up, warms up, times the --steps steps and prints the JSON line. --dump-outputs DIR writes what the last timed step
+returned (5b: `latent`, the updated [48,13,44,80] latent, and `pred`, the model's velocity on the 8 new frames) as DIR/<name>.npy in
+float32; the inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
 The JSON line also carries
-  roofline     : the kernel with the LARGEST share of the timed steps (every kernel group of the block is bracketed with HIP
-                 events on the launch stream inside the timed region; today that is the self-attention kernel), against the
-                 2.5 PFLOP/s dense bf16 MFMA peak; roofline_all lists the other groups the same way.
+  roofline     : the kernel with the LARGEST share of the timed steps (the last warmup step brackets every kernel group of the block with
+                 HIP events and names it; the timed steps bracket only that group; today it is the self-attention kernel), against the
+                 2.5 PFLOP/s dense bf16 MFMA peak.
+With --full (off by default) it runs everything else behind the timed steps and adds:
+  roofline_all : the other kernel groups the same way, from fully instrumented steps of their own.
+  cached_context_ms_per_step / trimmed_last_block_ms_per_step : the two engine options beside the headline, timed on steps of their own.
   cpu_baseline : the CPU oracle restatement of the reference (oracle/dit.py) timed on the host cores on a bounded
                  sample (one DiT block at the full L, extrapolated to 30 blocks), rank 0 / N=1 only.
   parity       : that same CPU block output against the device engine on identical inputs (rel-L2 / max-abs).
@@ -24,6 +31,7 @@ The JSON line also carries
                  VAE passes of the two pipelines (Wan2.2 17-frame encode, Wan2.1 decode / encode) with their own roofline fractions.
   calibration  : what THIS box sustains, measured right behind the timed steps (yume_amd/calibrate.py: pure-MFMA microkernel on random
                  operands + one fixed 8192^3 launch of the product GEMM); every MFMA-bound group carries frac_of_sustained next to frac.
+  workloads    : BASELINE.json configs[2] / [3] / [4] (below), each with a timed region of its own.
 
 --workload tts / longvideo / 14b run BASELINE.json configs[3] / [4] / [2] (see their functions); the default is configs[1].
 """
@@ -318,6 +326,28 @@ def _timed(fn, world):
     return r, float(dt.item())
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22          # elements kept of an array that would not fit the budget (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy in float32, at most DUMP_BUDGET_BYTES in all. An array past what is left of the
+    budget is written as out_dir/<name>_sample.npy: DUMP_SAMPLE of its flattened elements at indices drawn from a fixed seed (sorted)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in arrays.items():
+        flat = t.detach().float().reshape(-1)
+        if flat.numel() * 4 > left:
+            idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, left // 4),), generator=torch.Generator().manual_seed(0)).sort().values
+            flat, name, shape = flat[idx.to(flat.device)], name + "_sample", (-1,)
+        else:
+            shape = tuple(t.shape)
+        a = flat.cpu().numpy().reshape(shape)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def _build_5b(args, rank, dev):
     from yume_amd import distributed as ydist
     from yume_amd import synth
@@ -355,6 +385,8 @@ def bench_tts(args, rank, world, dev, built=None, emit=True):
     (latent, cp), dt = _timed(lambda: sampling.sde_tts_chunk(vel, latent, sig, lfz, histf, generator=g, i0=w0, i1=w1, current_pred=cp,
                                                              return_state=True), world)
     assert torch.isfinite(latent).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": latent, **({"current_pred": cp} if torch.is_tensor(cp) else {})})
     nfw = sampling.tts_forward_count(S, i0=w0, i1=w1)
     res = None
     if rank == 0:
@@ -393,7 +425,7 @@ def bench_longvideo(args, rank, world, dev, built=None, emit=True):
     g = torch.Generator(device=dev).manual_seed(4000 + rank)
     clip = torch.rand((3, 17, 704, 1280), generator=g, device=dev) * 2 - 1         # 17 frames -> 5 history latents
     ctxs = [torch.randn((77, 4096), generator=g, device=dev) for _ in range(args.chunks)]
-    Ls, dec_ms = [], []
+    Ls, dec_ms, last = [], [], {}
 
     def run(n_chunks, steps):
         hist = vae.encode([clip])[0]
@@ -402,10 +434,15 @@ def bench_longvideo(args, rank, world, dev, built=None, emit=True):
             Ls.append(plan.seq_len)
             hist, vids = sampling.long_video_5b(model, vae, hist, ctxs[k:k + 1], steps, shift, lfz, generator=g, decode=True)
             assert torch.isfinite(vids[0]).all()
+        if args.dump_outputs:
+            last["video"] = vids[0]
         return hist
     run(1, max(1, args.warmup))
     Ls.clear()
     hist, dt = _timed(lambda: run(args.chunks, args.steps), world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"history": hist, "video": last["video"]})
+    last.clear()
     # where a chunk's time goes (diagnostic pass behind the timed region, host clock with a synchronise between the parts)
     parts = {}
     if rank == 0:
@@ -495,6 +532,8 @@ def bench_14b(args, rank, world, dev, emit=True):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert torch.isfinite(latent).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": latent})
     tmax = torch.tensor([dt], dtype=torch.float64, device=_coll_dev(dev))
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -529,6 +568,7 @@ def other_workloads(args, dev, built):
                              ("longvideo", bench_longvideo, {"built": built}, dict(steps=8, warmup=1, chunks=8)),
                              ("14b", bench_14b, {}, dict(steps=3, warmup=1))):
         a = copy.copy(args)
+        a.dump_outputs = None                           # --dump-outputs holds the headline's arrays only
         for k, v in ov.items():
             setattr(a, k, v)
         try:
@@ -585,7 +625,9 @@ def _self_launch(args, share):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1",
            f"--nproc-per-node={n}", os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child process, not an exec of this one: device_count() above may already have brought up the HIP runtime here
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -608,6 +650,11 @@ def main():
                          "run as a subprocess behind the timed region)")
     ap.add_argument("--no-workloads", action="store_true",
                     help="5b only: do not attach BASELINE configs[2] / [3] / [4] (14B CFG, SDE/TTS, long video) as `workloads` to the JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="5b: also run everything beside the headline (roofline_all, calibration, cached-context / trimmed-block steps, VAE "
+                         "passes, CPU baselines, parity legs, the other workloads); off = set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))          # `torchrun --nproc-per-node N bench.py` alone means N ranks
@@ -673,12 +720,15 @@ def main():
     sig = synth.sampling_sigmas(steps_total, shift)
     zeros_hist = torch.zeros(plan.n_hist_tok, dtype=torch.float64, device=dev)
     ones_new = torch.ones(plan.n_new_tok, dtype=torch.float64, device=dev)
+    last_step, last = args.warmup + args.steps - 1, {}
 
     def step(i, latent):
         s = sig[i % steps_total]
         s_next = sig[i % steps_total + 1] if (i % steps_total) + 1 < steps_total else 0.0
         t = torch.cat([zeros_hist, ones_new * (s * 1000.0)]).unsqueeze(0)              # sample_5b.py:965-972
         pred = model([latent], t=t, context=context, seq_len=L, latent_frame_zero=lfz, flag=True)[0]
+        if i == last_step:
+            last["pred"] = pred                                                         # --dump-outputs: the last timed step's velocity
         new = latent[:, -lfz:] + (s_next - s) * pred                                    # :987-990
         return torch.cat([hist, new], dim=1)                                            # :1031-1034
 
@@ -708,8 +758,12 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof, model.engine.prof, model.engine.prof_only = model.engine.prof, None, None
+    assert torch.isfinite(latent).all(), "non-finite latents"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": latent, "pred": last.pop("pred")})
+    last.clear()
     n_extra, prof_all = 2, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         lat_x = latent
         model.engine.prof = prof_all
         for i in range(n_extra):
@@ -717,11 +771,10 @@ def main():
         torch.cuda.synchronize()
         model.engine.prof = None
         del lat_x
-    assert torch.isfinite(latent).all(), "non-finite latents"
     # per-box calibration, right behind the timed steps (same thermal / power state): what this chip sustains under a pure MFMA load and
     # on one fixed reference launch of the product GEMM (yume_amd/calibrate.py)
     calib = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from yume_amd import calibrate
             cm, cg = calibrate.mfma_sustained(dev), calibrate.gemm_reference(dev)
@@ -736,7 +789,7 @@ def main():
 
     # SURVEY §8(f).1 (step-invariant conditioning cached across steps): reported beside the headline, never as `value`
     cached_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         model.engine.cache_context = True
         lat2 = step(0, latent)
         torch.cuda.synchronize()
@@ -749,7 +802,7 @@ def main():
         del lat2
     # VERDICT r5 #6 (the last block's history rows supply K / V only): reported beside the headline like the cached context, never as `value`
     trimmed_ms = None
-    if rank == 0 and not sp:
+    if rank == 0 and not sp and args.full:
         model.engine.trim_last_block = True
         lat2 = step(0, latent)
         torch.cuda.synchronize()
@@ -762,7 +815,7 @@ def main():
         del lat2
 
     vae_res = None
-    if not args.no_vae and rank == 0:
+    if args.full and not args.no_vae and rank == 0:
         vae_res = vae_decode_rate(dev, latent[:, -lfz:].float())
 
     tmax = torch.tensor([dt], dtype=torch.float64, device=_coll_dev(dev))
@@ -798,23 +851,26 @@ def main():
                                    "lfz=8, L=9460), ODE Euler steps of a 50-step shift-7 schedule, no CFG, one chain per GPU",
                        "num_layers": cfg["num_layers"], "tokens": L, "parallelism": (f"sp{world} (one chain, Ulysses all-to-all, replicated weights)" if sp
                                        else f"dp{world} (independent chains, replicated weights)")},
-            "calibration": calib,
             "chain_checksums": checks, "weight_broadcast_collectives": n_bcast,
-            "vae_decode": vae_res,
-            "cached_context_ms_per_step": cached_ms,
-            "trimmed_last_block_ms_per_step": trimmed_ms,
             "host_threads_per_rank": threads_per_rank, "cpu_legs_started_at": cpu_legs_started_at,
             "model_tflop_per_step": flops_fwd_5b(L, n=cfg["num_layers"]) / 1e12,
             "model_tflops_per_gpu": flops_fwd_5b(L, n=cfg["num_layers"]) / 1e12 / (ms_per_step * 1e-3),
             "roofline": rl_all[0] if rl_all else None,          # the kernel group with the largest share of the step
-            "roofline_all": rl_all[1:],
-            "roofline_all_source": f"{n_extra} fully instrumented steps behind the timed region (HIP events around every kernel call); "
-                                   "the timed steps bracket only the dominant group",
         }
+        if args.full:
+            out.update({
+                "calibration": calib,
+                "vae_decode": vae_res,
+                "cached_context_ms_per_step": cached_ms,
+                "trimmed_last_block_ms_per_step": trimmed_ms,
+                "roofline_all": rl_all[1:],
+                "roofline_all_source": f"{n_extra} fully instrumented steps behind the timed region (HIP events around every kernel call); "
+                                       "the timed steps bracket only the dominant group",
+            })
         # cpu_baseline / parity are emitted by rank 0 at ANY world size (the CPU legs run on rank 0's host cores after the timed region;
         # the other ranks have nothing left to do and leave)
         job = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"], blk_par = cpu_baseline(cfg, L, model)
                 out["parity"] = {"block": blk_par}
@@ -834,7 +890,7 @@ def main():
                     job = (step_job.start_job("5b", "cond", job_out, threads=out["cpu_baseline"].get("cores") or 32), job_out)
                 except Exception as e:  # noqa: BLE001
                     out.setdefault("parity", {})["full_step"] = {"failed": str(e)}
-        if world == 1 and not args.no_workloads and not args.layers:
+        if world == 1 and args.full and not args.no_workloads and not args.layers:
             out["workloads"] = other_workloads(args, dev, (cfg, model, n_bcast))
         if job is not None:
             try:

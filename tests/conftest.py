@@ -25,9 +25,37 @@ def pytest_collection_modifyitems(config, items):
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 
-def load_golden(name):
+def load_golden_file(path, **kw):
+    """torch.load of a fixture; one larger than a committed file may be is stored as consecutive byte pieces <path>.000, <path>.001, ..."""
+    import glob
+    import io
     import torch
-    return torch.load(os.path.join(GOLDEN_DIR, name + ".pt"), weights_only=False)
+    if os.path.exists(path):
+        return torch.load(path, weights_only=False, **kw)
+    parts = sorted(glob.glob(glob.escape(path) + ".[0-9][0-9][0-9]"))
+    assert parts, f"fixture {path} is missing"
+    return torch.load(io.BytesIO(b"".join(open(p, "rb").read() for p in parts)), weights_only=False, **kw)
+
+
+def load_golden(name):
+    return load_golden_file(os.path.join(GOLDEN_DIR, name + ".pt"))
+
+
+def live_err(got, want):
+    """max-abs difference of `got` from an output of the reference stored by oracle/make_golden_live.py: the whole tensor, or (large
+    outputs) its seeded sample of elements, where the shape must match and the fp64 norm agree to 1e-5 of itself"""
+    got = got.detach().cpu()
+    if "full" in want:
+        assert got.shape == want["full"].shape, (tuple(got.shape), tuple(want["full"].shape))
+        return (got.double() - want["full"].double()).abs().max().item()
+    assert tuple(got.shape) == tuple(want["shape"]), (tuple(got.shape), want["shape"])
+    assert abs(got.double().norm().item() - want["norm"]) <= 1e-5 * want["norm"]
+    return (got.reshape(-1)[want["idx"].long()].double() - want["values"].double()).abs().max().item()
+
+
+def live_max_abs(want):
+    """max |element| of a stored reference output (over its sample, for a sampled one)"""
+    return (want["full"] if "full" in want else want["values"]).abs().max().item()
 
 
 # ---------------------------------------------------------------------------------------------- full-depth oracle jobs (row N1)

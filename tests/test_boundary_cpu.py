@@ -8,7 +8,7 @@ from copy import deepcopy
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
 
 sys.path.insert(0, ROOT)
 from yume_amd import synth  # noqa: E402
@@ -87,7 +87,7 @@ def test_from_pretrained_streams_shards_and_reports_bad_keys(tmp_path):
 
 def test_prompt_cleaning_matches_reference_wrapper(monkeypatch):
     """wan/modules/tokenizers.py:12-22,75-77 (clean='whitespace'). ftfy is not installed in this image: its absence must be loud; with a
-    stand-in module the html / whitespace steps are checked against the reference's own functions when the tree is here."""
+    stand-in module the html / whitespace steps are checked against what the reference's own functions return (tests/golden/live_misc.pt)."""
     from yume_amd import t5
     monkeypatch.setitem(sys.modules, "ftfy", None)
     with pytest.raises(RuntimeError, match="ftfy"):
@@ -97,12 +97,8 @@ def test_prompt_cleaning_matches_reference_wrapper(monkeypatch):
     monkeypatch.setitem(sys.modules, "ftfy", fake)
     raw = "  A &amp;amp; B\n\n walks   through\tthe cityâ€™s  &lt;gate&gt;  "
     assert t5.clean_prompt(raw) == "A & B walks through the city's <gate>"
-    ref_file = "/root/reference/wan/modules/tokenizers.py"
-    if os.path.exists(ref_file):
-        src = open(ref_file).read().split("class HuggingfaceTokenizer")[0].replace("from transformers import AutoTokenizer", "")
-        ns = {}
-        exec(compile(src, ref_file, "exec"), ns)               # basic_clean / whitespace_clean of the reference, with the stand-in ftfy
-        assert ns["whitespace_clean"](ns["basic_clean"](raw)) == t5.clean_prompt(raw)
+    # basic_clean / whitespace_clean of the reference with the same stand-in ftfy (oracle/make_golden_live.py)
+    assert load_golden("live_misc")["clean"]["mojibake_quote"][raw] == t5.clean_prompt(raw)
 
 
 def test_attention_plan_workspace_sizes():
@@ -151,29 +147,14 @@ def test_model_pickles_and_rebinds_its_blocks(family):
 
 
 def test_clean_prompt_matches_the_reference_cleaners():
-    """yume_amd.t5.clean_prompt against the reference's own basic_clean + whitespace_clean (wan/modules/tokenizers.py:12-22), executed
-    from the reference file with ftfy.fix_text stubbed to the identity on BOTH sides (ftfy is not in this image; requirements.txt
-    declares it) — the html / whitespace arithmetic is what is compared."""
-    ref = "/root/reference/wan/modules/tokenizers.py"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
+    """yume_amd.t5.clean_prompt against the reference's own basic_clean + whitespace_clean (wan/modules/tokenizers.py:12-22), as
+    executed from the reference file with ftfy.fix_text stubbed to the identity on BOTH sides (ftfy is not in this image; requirements.txt
+    declares it) — the html / whitespace arithmetic is what is compared. The reference's results: tests/golden/live_misc.pt
+    (oracle/make_golden_live.py)."""
     from yume_amd.t5 import clean_prompt
-    src = open(ref).read()
-    ns = {}
-    stub = types.ModuleType("ftfy")
-    stub.fix_text = lambda t: t
-    saved = sys.modules.get("ftfy")
-    sys.modules["ftfy"] = stub
-    try:
-        head = src.split("class HuggingfaceTokenizer")[0].replace("from transformers import AutoTokenizer", "")
-        exec(compile(head, ref, "exec"), ns)
-    finally:
-        if saved is None:
-            del sys.modules["ftfy"]
-        else:
-            sys.modules["ftfy"] = saved
+    want = load_golden("live_misc")["clean"]["identity"]
     for t in ["  a  cat &amp;amp; a\tdog \n\n walk  ", "&lt;b&gt;bold&lt;/b&gt;", "", "  ", "x", "café   au   lait", "a&nbsp;b"]:
-        assert clean_prompt(t, fix_text=lambda s: s) == ns["whitespace_clean"](ns["basic_clean"](t)), repr(t)
+        assert clean_prompt(t, fix_text=lambda s: s) == want[t], repr(t)
     try:
         import ftfy  # noqa: F401
     except ImportError:

@@ -74,16 +74,22 @@ def _worker(rank, world, port, n_prompts, out_dir):
     dist.destroy_process_group()
 
 
+def _want_worker(_, n_prompts, out_dir):
+    net = TinyNet(seed=100)
+    with torch.no_grad():
+        torch.save(torch.stack([chain(net, 1000 + i) for i in range(n_prompts)]), os.path.join(out_dir, "want.pt"))
+
+
 def test_two_rank_sharded_sampling(tmp_path):
     world, n_prompts = 2, 4
     mp.spawn(_worker, args=(world, _free_port(), n_prompts, str(tmp_path)), nprocs=world, join=True)
     gathered = torch.load(os.path.join(tmp_path, "gathered.pt"))
-    net = TinyNet(seed=100)
-    with torch.no_grad():
-        for i in range(n_prompts):
-            want = chain(net, 1000 + i)
-            got = gathered[i % world, i // world]
-            assert torch.equal(got, want), i
+    # the single-process chains run in a fresh process like the ranks: this one's global torch state may have been changed by earlier tests
+    mp.spawn(_want_worker, args=(n_prompts, str(tmp_path)), nprocs=1, join=True)
+    wants = torch.load(os.path.join(tmp_path, "want.pt"))
+    for i in range(n_prompts):
+        got = gathered[i % world, i // world]
+        assert torch.equal(got, wants[i]), i
 
 
 def test_single_process_helpers_are_noops():

@@ -124,7 +124,7 @@ def test_bench_gpus_8_launches_eight_ranks_itself(tmp_path):
     barrier-bracketed timing, max over ranks, one JSON line from rank 0 — and the host-side rules of DESIGN §6: every rank caps its thread
     team at cpu_count // 8 (<= 16), and rank 0's CPU legs (cpu_baseline, parity) start only after every rank's GPU work is over."""
     import json
-    r, line = _run_bench(["--gpus", "8", "--layers", "1", "--steps", "2", "--warmup", "1", "--no-vae"],
+    r, line = _run_bench(["--gpus", "8", "--layers", "1", "--steps", "2", "--warmup", "1", "--no-vae", "--full"],
                          {"YUME_BENCH_SHARE_GPU": "1", "YUME_BENCH_RANK_LOG": str(tmp_path)}, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert line is not None, r.stdout[-2000:]

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import ROOT, load_golden, load_golden_file
 
 sys.path.insert(0, ROOT)
 from oracle import frames as oframes  # noqa: E402
@@ -71,7 +71,7 @@ def test_tiled_decode_overlap_matches_reference_outputs():
     import os
     from oracle.make_golden_tiled import FakeVae
     from yume_amd.video import tiled_decode_overlap, _tile_spans
-    cases = torch.load(os.path.join(ROOT, "tests", "golden", "tiled_decode.pt"))
+    cases = load_golden_file(os.path.join(ROOT, "tests", "golden", "tiled_decode.pt"))
     assert len(cases) == 5
     for cs in cases:
         got = tiled_decode_overlap(FakeVae(), cs["z"], n_tiles=cs["n_tiles"], image_overlap_size=cs["image_overlap_size"],
@@ -98,10 +98,10 @@ def _webapp_fixture():
     return v, fx["frames"].numpy()
 
 
-@pytest.mark.skipif(not ref_scripts.available(), reason="needs the reference tree (build container only)")
 def test_webapp_conversion_restated_equals_the_reference_function_live():
+    """the reference function's frames on this clip: tests/golden/live_misc.pt (oracle/make_golden_live.py)"""
     v = ref_scripts.webapp_case()
-    want = ref_scripts.run_webapp_postprocess(v.clone())
+    want = load_golden("live_misc")["webapp"]["frames"].numpy()
     assert want.dtype == np.uint8 and want.shape == (v.shape[1], v.shape[2], v.shape[3], v.shape[0])
     assert np.array_equal(oframes.frames_u8_webapp(v), want)
     # it is NOT the diffusers conversion: truncation vs round-half-even differ on most samples

@@ -5,10 +5,10 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT, load_golden
+from conftest import ROOT, live_err, live_max_abs, load_golden
 
 sys.path.insert(0, ROOT)
-from oracle import clip as oclip, ref_import  # noqa: E402
+from oracle import clip as oclip  # noqa: E402
 from yume_amd import clip, synth  # noqa: E402
 
 
@@ -20,17 +20,14 @@ def test_oracle_matches_reference_golden():
         assert (got - fx[key]).abs().max() <= 2e-5 * fx[key].abs().max()
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present")
 def test_oracle_matches_reference_class_directly():
+    """the reference VisionTransformer's output on these inputs: tests/golden/live_misc.pt (oracle/make_golden_live.py)"""
     cfg = synth.tiny_clip_cfg(dim=160, heads=2, layers=2, image=42)
     sd = synth.make_clip_state_dict(cfg, 2)
-    ref = ref_import.ref_clip().VisionTransformer(**cfg).eval()
-    ref.load_state_dict(sd, strict=True)
+    want = load_golden("live_misc")["clip"]["out31"]
     x = torch.randn(1, 3, 42, 42, generator=torch.Generator().manual_seed(3))
-    with torch.no_grad():
-        want = ref(x, use_31_block=True)
     got = oclip.visual_forward(sd, cfg, x, True)
-    assert (got - want).abs().max() <= 2e-5 * want.abs().max()
+    assert live_err(got, want) <= 2e-5 * live_max_abs(want)
 
 
 def test_dropin_has_the_reference_parameter_names():

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
 
 sys.path.insert(0, ROOT)
 from oracle import sampler as osamp  # noqa: E402
@@ -100,30 +100,36 @@ def _replay(seed, dtype):
     return lambda shape: torch.randn(shape, generator=g, dtype=dtype)
 
 
-@pytest.mark.skipif(not ref_scripts.available(), reason="needs the reference tree (build container only)")
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 def test_oracle_sampler_is_bit_identical_to_the_reference_scripts_live(dtype):
-    """oracle/sampler.py against sample_tts.py / sample.py / sample_5b.py's OWN loops executed here: same bits, same number of model
-    calls in the same order, and the 5B script's per-token timestep vector is zeros on the history tokens, 1000*sigma_i behind them."""
+    """oracle/sampler.py against what sample_tts.py / sample.py / sample_5b.py's OWN loops computed on these inputs (oracle/make_golden_live.py
+    -> tests/golden/live_sampler.pt): same results, same model calls in the same order, and the 5B script's per-token timestep vector is
+    zeros on the history tokens, 1000*sigma_i behind them. The results were bit-identical where the fixture was made; on another CPU
+    tanh / einsum may round differently in the last bit, so they are held to the tolerance of the fixture test below."""
     fx = torch.load(GOLD, weights_only=False)
+    live = load_golden("live_sampler")[str(dtype).split(".")[-1]]
     c, f, mi, noise, lfz = _script_inputs(fx, dtype)
+    tol = dict(rtol=0, atol=1e-10) if dtype == torch.float64 else dict(rtol=0, atol=1e-4)
+    same = lambda a, b: a.dtype == b.dtype and a.shape == b.shape and torch.allclose(a, b, **tol)
     sig3 = list(osamp.get_sampling_sigmas(50, 3.0))
     for sde in (True, False):
-        ref, draws, calls, span = ref_scripts.run_tts(f, noise.clone(), noise, mi, sig3, lfz, sde=sde, seed=fx["seed_noise"])
+        r = live[("tts", sde)]
         seen = []
         got = osamp.tts(lambda l, i, w: (seen.append((i, w)), f(l, i, w))[1], noise.clone(), mi, noise, sig3, lfz,
                         _replay(fx["seed_noise"], dtype), sde=sde)
-        assert torch.equal(got, ref) and seen == calls and len(calls) == 148 and len(draws) == (74 if sde else 0)
+        assert same(got, r["latent"]) and seen == r["calls"] and len(seen) == 148 and r["n_draws"] == (74 if sde else 0)
     for n in (50, 6):
         sig = list(osamp.get_sampling_sigmas(n, 3.0))
-        ref, calls, _ = ref_scripts.run_euler_14b(f, noise.clone(), noise, mi, sig, lfz)
-        assert torch.equal(osamp.euler_14b(f, noise.clone(), mi, noise, sig, lfz), ref) and len(calls) == 2 * n
+        r = live[("euler_14b", n)]
+        assert same(osamp.euler_14b(f, noise.clone(), mi, noise, sig, lfz), r["latent"]) and r["n_calls"] == 2 * n
         sig = list(osamp.get_sampling_sigmas(n, 7.0))
         lat0 = torch.cat([mi[:, :-lfz], noise[:, -lfz:]], dim=1)
         n0 = (c["F"] - lfz) * (c["H"] // 2) * (c["W"] // 2)
         seq_len = c["F"] * (c["H"] // 2) * (c["W"] // 2) + 5
-        ref, tvecs, calls, _ = ref_scripts.run_euler_5b(f, lat0.clone(), mi, sig, lfz, seq_len)
-        assert torch.equal(osamp.euler_5b(f, lat0.clone(), mi, sig, lfz), ref) and len(calls) == n
+        r = live[("euler_5b", n)]
+        assert same(osamp.euler_5b(f, lat0.clone(), mi, sig, lfz), r["latent"]) and r["n_calls"] == n
+        tvecs = r["tvecs"].unsqueeze(1)
+        assert len(tvecs) == n
         for i, t in enumerate(tvecs):
             want = torch.cat([torch.zeros(n0, dtype=torch.float64), torch.ones(seq_len - n0, dtype=torch.float64) * (sig[i] * 1000)])
             assert t.shape == (1, seq_len) and t.dtype == torch.float64 and torch.equal(t[0], want)

@@ -1,8 +1,8 @@
 #!/bin/bash
-# A/B of environment switches on the default bench (quick form: no CPU legs, no VAE, no side workloads). usage: tools/bench_ab.sh "VAR=a" "VAR=b" ...
+# A/B of environment switches on the full bench (quick form: no CPU legs, no VAE, no side workloads). usage: tools/bench_ab.sh "VAR=a" "VAR=b" ...
 export TMPDIR=/tmp
 for kv in "$@"; do
-  env $kv python bench.py --no-cpu-baseline --no-vae --no-workloads --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > /tmp/ab.json
+  env $kv python bench.py --full --no-cpu-baseline --no-vae --no-workloads --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > /tmp/ab.json
   python - "$kv" <<'PY'
 import json, sys
 d = json.loads(open('/tmp/ab.json').read())
