@@ -38,7 +38,7 @@ extern "C" {
 /* ---- library info ------------------------------------------------------------------- */
 const char* yume_last_error(void);
 /* ABI version of this header; bumped on any signature change (yume_amd/_lib.py refuses a library that reports another one). */
-#define YUME_ABI_VERSION 8
+#define YUME_ABI_VERSION 9
 int yume_abi_version(void);
 /* name of the gfx target the kernels were compiled for ("gfx950"). */
 const char* yume_target_arch(void);
@@ -211,6 +211,28 @@ int64_t yume_attn_workspace_bytes(int64_t Lq, int64_t Lk, int64_t H);
 int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
                      void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale,
                      int accumulate, int variant, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same call with a WEIGHTED LAST KEY: key Lk-1 stands for `last_key_weight` identical keys,
+ *   O[h,i,:] = sum_j w_j e^{scale <Q_i,K_j>} V_j / sum_j w_j e^{scale <Q_i,K_j>},   w_j = 1 for j < Lk-1,  w_{Lk-1} = last_key_weight
+ * replaces: the reference's un-masked 512-key cross-attention over a zero-padded prompt (wan23/modules/model.py:815-821 with
+ *           context_lens = None, wan/modules/model.py:931-936; wan/modules/t5.py:511-513 trims each prompt to its real length first). A zero
+ *           row through text_embedding is a constant vector, so keys n .. 511 of an n-token prompt are copies of one key: softmax over
+ *           n real keys and m copies of key p equals softmax over n + 1 keys in which key p counts m times. Nothing is approximated; a run
+ *           of repeated keys anywhere else can be folded the same way by putting it last.
+ * last_key_weight: by value (a captured graph needs no extra device memory); finite and in [1, 2^20], YUME_EINVAL otherwise. With
+ *    YUME_ATTN_Q_PRESCALED the meaning is the same (the weight multiplies 2^s). The kernels multiply the last key's exponential (one bf16
+ *    rounding of w e^s before the P V product); the running-base logic sees the plain score.
+ * last_key_weight == 1 is exactly yume_attn_fwd_ws: same kernel choice, same bits. A weight != 1 is served by
+ *    variant 10 = the short-key kernel (attn_short.hpp, r7: Lk <= 128, a head's K and V^T resident in one wave's registers, exact single-pass
+ *                 softmax, no LDS, no workspace; also needs ldo % 8 == 0 and a 16-byte aligned O; selectable at any weight), and
+ *    variant 2  = the 4-wave LDS-DMA kernel, any Lk (the last key tile takes the masked body, also when Lk % 64 == 0);
+ *    variant 0  = the short-key kernel where it applies (Lk <= 128, ldo % 8 == 0, 16-byte aligned O: measured 1.6-1.9 x faster than variant 2
+ *                 on both cross-attention shapes, profiles/r7_dedup_pad_keys.md; env YUME_ATTN_SHORT=0 keeps variant 0 off it for A/B runs),
+ *                 otherwise variant 2 — also for Lk >= 1536;
+ *    variants 1, 4, 7, 8, 9 return YUME_EUNSUP (the message names the variant).
+ * accumulate, ragged Lq, both scale modes and YUME_ATTN_KV_PADDED as above. The workspace is not used by a weighted call. */
+int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                     void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale,
+                     int accumulate, int variant, void* workspace, int64_t workspace_bytes, float last_key_weight, void* stream);
 
 /* ---- small-M fp32 linear (time embedding MLP) ---------------------------------------------
  * replaces: wan23/modules/model.py:459-461,803-812 (time_embedding, time_projection under

@@ -20,7 +20,7 @@ s = s.replace("⟨ATTN8⟩", f"{a['launch_ms']:.4f} ms per 5B launch (kernel + m
               f"{a['share_of_step'] * 100:.0f} % of the step; fabric traffic {a['traffic'] / 1e6:.0f} MB vs 232 MB algorithmic ({a['traffic'] / 232.5e6:.2f} ×; `profiles/r4_pmc_traffic_attention_v8.csv`: "
               "MFMA busy 66.9 % at 1.75 GHz on random data)")
 x = g["attn_cross"]
-s = s.replace("⟨ATTNX⟩", f"{pf('attn_cross')}; {x['ms_per_step']:.1f} ms per step" + (f"; fabric traffic {x['traffic'] / 1e6:.0f} MB vs 65 MB algorithmic" if x.get("traffic") else ""))
+s = s.replace("⟨ATTNX⟩", f"{pf('attn_cross')}; {x['ms_per_step']:.1f} ms per step" + (f"; fabric traffic {x['traffic'] / 1e6:.0f} MB vs 122.5 MB algorithmic (Q 58 + K / V^T 6.3 read, O 58 written)" if x.get("traffic") else ""))
 s = s.replace("⟨GEMM⟩", "; ".join(f"{n[5:]} {pf(n)}" for n in ("gemm_qkv", "gemm_ffn0", "gemm_ffn2", "gemm_cross_q", "gemm_o", "gemm_cross_o")))
 v = d.get("vae_decode") or {}
 s = s.replace("⟨CONV⟩", f"Wan2.2 chunk decode {v.get('ms_per_chunk', float('nan')):.1f} ms = {v.get('latents_per_s', float('nan')):.1f} latents/s = {v.get('tflops', float('nan')) / 1e3:.2f} PF average")

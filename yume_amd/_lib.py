@@ -35,6 +35,7 @@ SIGNATURES = {
     "yume_attn_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _P],
     "yume_attn_workspace_bytes": [_L, _L, _L],
     "yume_attn_fwd_ws": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _P, _L, _P],
+    "yume_attn_fwd_kw": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _P, _L, _F, _P],
     "yume_linear_smallm_f32": [_P, _L, _L, _P, _I, _P, _L, _I, _I, _P, _P, _P],
     "yume_sinusoidal_embed": [_P, _P, _L, _L, _P, _P],
     "yume_modulation_table": [_P, _P, _L, _L, _L, _P, _P],
@@ -57,7 +58,7 @@ _RES = {"yume_last_error": c_char_p, "yume_target_arch": c_char_p, "yume_gemm_sp
         "yume_counter_workspace_bytes": c_int64, "yume_gemm_workspace_bytes": c_int64}
 
 _lib = None
-ABI_VERSION = 8          # must equal YUME_ABI_VERSION in include/yume_hip.h; bumped whenever an argument list changes
+ABI_VERSION = 9          # must equal YUME_ABI_VERSION in include/yume_hip.h; bumped whenever an argument list changes
 
 
 def load():

@@ -21,6 +21,9 @@ struct AttnArgs {
     // v7 kernel only: query blocks >= tail_qb are cut into `splits` key ranges inside the same launch (their pieces are dispatched
     // after the whole blocks and fill the partial last round of workgroups); partials as above with rows = Lq - (q_lo + 256*tail_qb)
     int tail_qb, splits;
+    // yume_attn_fwd_kw: the LAST key (Lk - 1) counts last_w times (its exponential is multiplied by it); exactly 1 on every other call.
+    // Read by attn_fwd_kernel_v2<true> and attn_short.hpp only
+    float last_w;
 };
 
 // attn_fwd7.hip: 4-wave / 64-queries-per-wave kernel (one wave per SIMD, 512 registers); grid = ceil(H/8) * nqb * 8 blocks

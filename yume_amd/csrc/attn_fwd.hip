@@ -6,6 +6,9 @@
 //   attn_fwd_kernel_v2  4 waves, 128 queries, two workgroups per CU, K / V^T tiles by LDS-DMA (cross-attention and the
 //                       query rows left over after whole rounds of v4 workgroups)
 //   attn_fwd_kernel     as v2 with register-staged tiles (the first version; kept as an independent cross-check)
+// and two take a WEIGHTED LAST KEY (yume_attn_fwd_kw, r7: key Lk - 1 stands for last_key_weight identical keys):
+//   attn_fwd_kernel_v2<true>    the 4-wave kernel with the weight on the last key's exponential (any Lk)
+//   attn_short_kernel           Lk <= 128: a head's K and V^T resident in one wave's registers (attn_short.hpp)
 // Common to all: each wave owns 32 queries and walks the keys in tiles of 64. Everything is computed TRANSPOSED so that
 // the softmax row of a query lives in ONE lane (plus its partner lane^32) and never needs LDS or cross-lane shuffles:
 //
@@ -25,6 +28,8 @@
 #include "counters.hpp"
 #include "trace.hpp"
 #include "attn_cross_rk.hpp"
+#include "attn_short.hpp"
+#include <math.h>
 
 namespace {
 
@@ -338,7 +343,7 @@ __device__ __forceinline__ void stage_store_v2(const Stage& s, char* buf, int ti
     }
 }
 
-template <bool MASK>
+template <bool MASK, bool KW = false>
 __device__ __forceinline__ void tile_body_v2(const char* kb, const AttnArgs& p, const bf16x8_t (&qf)[8],
                                              f32x16 (&oacc)[4], float& m_run, float& l_run, int j0, int ql, int hi,
                                              const int (&koff)[8], const int (&voff)[4]) {
@@ -397,6 +402,7 @@ __device__ __forceinline__ void tile_body_v2(const char* kb, const AttnArgs& p, 
             if (MASK) {
                 const int key = j0 + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 pv = key < p.Lk ? pv : 0.f;
+                if (KW) pv = key == p.Lk - 1 ? pv * p.last_w : pv;      // the weighted last key: the exponential is multiplied, the base logic sees the plain score
             }
             sacc[b][r] = pv;
             psum += pv;
@@ -442,6 +448,9 @@ __device__ __forceinline__ void tile_body_v2(const char* kb, const AttnArgs& p, 
     }
 }
 
+// KW: the last key carries p.last_w (yume_attn_fwd_kw). The last tile then takes the MASK body also when Lk % 64 == 0 (it still comes by LDS-DMA:
+// only a ragged tile is register-staged). KW = false is the kernel as it always was.
+template <bool KW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel_v2(AttnArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * V2_BUF];
     const int tid = threadIdx.x;
@@ -514,8 +523,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel_v2(AttnArgs p) {
         const bool has_next = t + 1 < t1;
         const bool next_reg = has_next && ragged && (t + 2 == nt);
         if (has_next && !next_reg) dma_tile(dp, kstep, nb, wave);
-        if (t == nt - 1 && ragged)
-            tile_body_v2<true>(kb, p, qf, oacc, m_run, l_run, t * KT, ql, hi, koff, voff);
+        if (t == nt - 1 && (ragged || KW))
+            tile_body_v2<true, KW>(kb, p, qf, oacc, m_run, l_run, t * KT, ql, hi, koff, voff);
         else
             tile_body_v2<false>(kb, p, qf, oacc, m_run, l_run, t * KT, ql, hi, koff, voff);
         if (next_reg) {
@@ -1071,6 +1080,11 @@ static bool attn8_enabled() {
     static const bool on = [] { const char* v = getenv("YUME_ATTN_V8"); return !v || atoi(v) != 0; }();
     return on;
 }
+#ifndef YUME_ATTN_SHORT_DEFAULT
+// measured (profiles/r7_dedup_pad_keys.md, Lk 78, last key x 435): 32.9 against 53.7 us on the 5B shape, 146.5 against 271.7 us on the 14B
+// shape for the 4-wave kernel: faster on both, so variant 0 takes the short-key kernel
+#define YUME_ATTN_SHORT_DEFAULT true
+#endif
 static int cu_count() {
     static thread_local int n[64] = {};
     int dev = 0;
@@ -1104,19 +1118,40 @@ static int64_t attn8_workspace(int64_t Lq, int64_t Lk, int64_t H) {
     return (int64_t)pl.splits * (Lq - pl.tail_qb * QB4) * (H * D + H * 2) * 4;
 }
 
-extern "C" int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
-                                void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate,
-                                int variant, void* workspace, int64_t workspace_bytes, void* stream);
+static int attn_fwd_impl(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo, int64_t Lq,
+                         int64_t Lk, int64_t H, float scale, int accumulate, int variant, void* workspace, int64_t workspace_bytes,
+                         float last_key_weight, void* stream);
 
 extern "C" int yume_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
                              void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate,
                              int variant, void* stream) {
-    return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, nullptr, 0, stream);
+    return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, nullptr, 0, 1.0f, stream);
 }
 
 extern "C" int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
                                 void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate,
                                 int variant, void* workspace, int64_t workspace_bytes, void* stream) {
+    return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, 1.0f, stream);
+}
+
+extern "C" int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                                void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate,
+                                int variant, void* workspace, int64_t workspace_bytes, float last_key_weight, void* stream) {
+    YUME_REQUIRE(isfinite(last_key_weight) && last_key_weight >= 1.0f && last_key_weight <= 1048576.0f,
+                 "attn_fwd_kw: last_key_weight=%g must be finite and in [1, 2^20]", (double)last_key_weight);
+    return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, last_key_weight, stream);
+}
+
+// variant 0 sends a weighted call with Lk <= 128 to the short-key kernel (attn_short.hpp): it measured faster than the 4-wave kernel on both
+// cross-attention shapes (the routing rule and the table: profiles/r7_dedup_pad_keys.md). YUME_ATTN_SHORT=0 keeps variant 0 on the 4-wave kernel (A/B runs).
+static bool attn_short_auto() {
+    static const bool on = [] { const char* v = getenv("YUME_ATTN_SHORT"); return v ? atoi(v) != 0 : YUME_ATTN_SHORT_DEFAULT; }();
+    return on;
+}
+
+static int attn_fwd_impl(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo, int64_t Lq,
+                         int64_t Lk, int64_t H, float scale, int accumulate, int variant, void* workspace, int64_t workspace_bytes,
+                         float last_key_weight, void* stream) {
     YUME_REQUIRE(Q && K && Vt && O, "attn_fwd: NULL pointer");
     YUME_REQUIRE(Lq > 0 && Lk > 0 && H > 0, "attn_fwd: empty problem Lq=%lld Lk=%lld H=%lld", (long long)Lq, (long long)Lk, (long long)H);
     YUME_REQUIRE(Lq < (1ll << 30) && Lk < (1ll << 30) && H < 65536, "attn_fwd: dimension too large");
@@ -1143,7 +1178,32 @@ extern "C" int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64
     a.part_ml = nullptr;
     a.tail_qb = 0;
     a.splits = 1;
+    a.last_w = last_key_weight;
     hipStream_t st = (hipStream_t)stream;
+    // a weighted last key (yume_attn_fwd_kw): the short-key kernel for Lk <= 128, the 4-wave LDS-DMA kernel for any Lk; the other kernels do
+    // not take a weight. last_key_weight == 1 changes nothing below.
+    const bool weighted = last_key_weight != 1.0f;
+    if (weighted && (variant == 1 || variant == 4 || variant == 7 || variant == 8 || variant == 9)) {
+        yume_set_error("attn_fwd_kw: variant %d does not take a last_key_weight != 1 (variants 0, 2 and 10 do)", variant);
+        return YUME_EUNSUP;
+    }
+    if (variant == 10) {
+        YUME_REQUIRE(Lk <= attn_short::LKMAX, "attn_fwd: variant 10 (short-key kernel) needs Lk <= 128, got Lk=%lld", (long long)Lk);
+        YUME_REQUIRE(attn_short::fits(Lk, ldo, O), "attn_fwd: variant 10 (short-key kernel) needs ldo %% 8 == 0 and a 16-byte aligned O");
+    }
+    if (variant == 10 || (weighted && variant == 0 && attn_short_auto() && attn_short::fits(Lk, ldo, O))) {
+        attn_short::launch(a, cu_count(), st);
+        YUME_CHECK_LAUNCH("attn_fwd");
+        return YUME_OK;
+    }
+    if (weighted) {            // variant 0 / 2, any Lk (also Lk >= 1536): attn_fwd_kernel_v2<true> over all query rows
+        AttnArgs b = a;
+        b.nqb = (int)((Lq + QB - 1) / QB);
+        b.tail_qb = b.nqb;
+        hipLaunchKernelGGL(attn_fwd_kernel_v2<true>, dim3((unsigned)(((H + 7) / 8) * b.nqb * 8)), dim3(NW * 64), 0, st, b);
+        YUME_CHECK_LAUNCH("attn_fwd");
+        return YUME_OK;
+    }
     // launch one kernel over the query rows [lo, hi)
     auto run = [&](int kernel, int64_t lo, int64_t hi) {
         AttnArgs b = a;
@@ -1162,7 +1222,7 @@ extern "C" int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64
         else if (kernel == 1)
             hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(NW * 64), 0, st, b);
         else
-            hipLaunchKernelGGL(attn_fwd_kernel_v2, grid, dim3(NW * 64), 0, st, b);
+            hipLaunchKernelGGL(attn_fwd_kernel_v2<false>, grid, dim3(NW * 64), 0, st, b);
     };
     // the persistent kernel (attn_fwd8.hip): base-free body only, K / V^T padded to whole key tiles (the caller's word: YUME_ATTN_KV_PADDED;
     // ldvt can be checked), a registered counter workspace for its tickets. variant 8 insists on it, variant 0 takes it where it applies.

@@ -50,8 +50,16 @@ class DiTEngine:
         # projection, cross-attention and FFN are not computed (5B: 2420 of 9460 rows of one block). The returned velocity is unchanged
         # (GEMM / attention rows are independent). Off by default = the reference's work; bench.py reports it beside the headline.
         self.trim_last_block = os.environ.get("YUME_TRIM_LAST_BLOCK", "0") == "1"
+        # r7: both families pad the prompt with ZERO rows up to text_len before text_embedding and attend over all text_len keys without a
+        # key mask (wan23/modules/model.py:815-821, wan/modules/model.py:931-936). A zero row through Linear -> GELU -> Linear is one constant
+        # vector, so for an n-token prompt the rows n .. text_len-1 of the embedded context, and of every block's cross-attention K and V, are
+        # copies of one row. With dedup_pad_keys the engine embeds and projects n + 1 rows (the prompt and ONE zero row) and every text
+        # cross-attention runs over n + 1 keys whose last one counts text_len - n times (yume_attn_fwd_kw): the same softmax, nothing
+        # approximated, only the order of a few roundings changes. Off by default = the reference's work; env YUME_DEDUP_PAD_KEYS=1 turns it on.
+        self.dedup_pad_keys = os.environ.get("YUME_DEDUP_PAD_KEYS", "0") == "1"
         # kernel selection passed to every GEMM / attention call: 0 = automatic (product setting); tests set (1, 1) to run the
-        # whole model on the independent 128x128-tile GEMM and register-staged attention kernels as a cross-check
+        # whole model on the independent 128x128-tile GEMM and register-staged attention kernels as a cross-check (the register-staged
+        # attention kernel takes no key weight: with dedup_pad_keys the text cross-attention of that mode runs variant 2)
         self.gemm_variant = 0
         self.attn_variant = 0
         # self-attention q leaves yume_rmsnorm_rope already multiplied by softmax scale * log2(e) (folded into the fp32 RMSNorm weight of q,
@@ -240,17 +248,21 @@ class DiTEngine:
         return e, e0
 
     def _text_ctx(self, context, out_rows):
+        """text_embedding of the prompt padded with zero rows to out_rows' row count: text_len, or n + 1 with dedup_pad_keys (one zero row
+        stands for all the pad rows; its weight goes to the attention calls)."""
         m = self.model
         w0, b0, w2, b2 = self.P["text"]
         n = context.shape[0]
         if n > m.text_len:
             raise RuntimeError(f"context has {n} tokens > text_len {m.text_len}")
-        cpad = self._buf("ctx_in", (m.text_len, m.text_dim), torch.bfloat16)
+        rows = out_rows.shape[0]
+        sfx = "" if rows == m.text_len else f"_{rows}"
+        cpad = self._buf("ctx_in" + sfx, (rows, m.text_dim), torch.bfloat16)
         if n:
             ops.cast_bf16(context.to(device=self.dev, dtype=torch.float32).contiguous(), n, cpad)
         else:
             cpad.zero_()                       # empty prompt: the reference pads [0, text_dim] to text_len zero rows (model.py:816-821)
-        hid = self._buf("ctx_hid", (m.text_len, m.dim), torch.bfloat16)
+        hid = self._buf("ctx_hid" + sfx, (rows, m.dim), torch.bfloat16)
         ops.gemm_bf16(cpad, w0, b0, hid, EPI_BF16_GELU, variant=self.gemm_variant)
         ops.gemm_bf16(hid, w2, b2, out_rows, EPI_BF16, variant=self.gemm_variant)
 
@@ -281,8 +293,10 @@ class DiTEngine:
             ops.rmsnorm_rows_periodic(kc.view(nk * nb, C), C, nk_w, self.qk_eps)
         return kc, vct
 
-    def _blocks(self, xs, L, tab, row_idx, R, rope, n_rope, ctx, n_img, ctx_fresh=True, n_keys=None, only=None, cache=None, n_trim=0):
+    def _blocks(self, xs, L, tab, row_idx, R, rope, n_rope, ctx, n_img, ctx_fresh=True, n_keys=None, only=None, cache=None, n_trim=0,
+                txt_last_weight=1.0):
         """xs fp32 [L, C] in/out. tab fp32 [nb, R, 6, C]; rope fp32 [n_rope, 64, 2] (n_rope == L here).
+        txt_last_weight: how many keys the LAST text row of ctx stands for (dedup_pad_keys: text_len - n; 1 = every row is one key).
         n_trim: the first n_trim rows of the LAST block's output are not needed by the caller (history tokens in front of the head): that
         block computes K / V for every row but everything behind the QKV projection for the rows [n_trim, L) only; xs[:n_trim] is then stale.
         With sequence parallelism L is this rank's (padded) chunk and n_keys the true global token count.
@@ -304,6 +318,8 @@ class DiTEngine:
         if n_img:
             kc_i, vct_i = self._cross_kv("i", ctx[:n_img], n_img, self.P["wkv_i"], self.P["bkv_i"], self.P["nk_i"], ctx_fresh)
         T = self._timed
+        # (the register-staged kernel of the cross-check mode takes no key weight: variant 2 then)
+        txt_variant = 2 if (txt_last_weight != 1.0 and self.attn_variant == 1) else self.attn_variant
         ids = range(len(self.P["blocks"])) if only is None else only
         for j, i in enumerate(ids):
             d = self.P["blocks"][i]
@@ -319,7 +335,7 @@ class DiTEngine:
             s = n_trim if j == len(ids) - 1 else 0                      # rows [s, L) are the ones whose output is wanted
             if s:
                 self._trimmed_block(xs, L, s, d, i, tb, ts, row_idx, rope, eps, h, qk, vt, att, ff, kc_t, vct_t, ntxt,
-                                    (kc_i, vct_i, n_img) if n_img else None)
+                                    (kc_i, vct_i, n_img) if n_img else None, txt_last_weight, txt_variant)
                 continue
             # --- self attention
             T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, row_idx, True, h, 0, eps)
@@ -348,8 +364,8 @@ class DiTEngine:
                 ops.cast_bf16(xs, L, h)
             T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:, :C], EPI_BF16, variant=self.gemm_variant)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:, :C], C, 1, d["nq_c"], self.qk_eps)
-            T("attn_cross", ops.attn_fwd, qk[:, :C], kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], att, L, ntxt, H, variant=self.attn_variant,
-              q_prescaled=self.q_prescale, kv_padded=True)
+            T("attn_cross", ops.attn_fwd, qk[:, :C], kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], att, L, ntxt, H, variant=txt_variant,
+              q_prescaled=self.q_prescale, kv_padded=True, last_key_weight=txt_last_weight)
             if n_img:
                 T("attn_cross", ops.attn_fwd, qk[:, :C], kc_i[:, i * C:(i + 1) * C], vct_i[i * C:(i + 1) * C], att, L, n_img, H, accumulate=True,
                   variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
@@ -361,7 +377,8 @@ class DiTEngine:
             if cache is not None and cache[0] == "record" and i in cache[1]:
                 cache[2].append((xs - x_in).to(torch.bfloat16).unsqueeze(0))     # reference keeps [B, L, C] bf16
 
-    def _trimmed_block(self, xs, L, s, d, i, tb, ts, row_idx, rope, eps, h, qk, vt, att, ff, kc_t, vct_t, ntxt, img):
+    def _trimmed_block(self, xs, L, s, d, i, tb, ts, row_idx, rope, eps, h, qk, vt, att, ff, kc_t, vct_t, ntxt, img, txt_last_weight=1.0,
+                       txt_variant=0):
         """the block of _blocks with everything behind the QKV projection restricted to the rows [s, L) (trim_last_block): the same
         kernel calls on row-offset views, so the rows that are computed go through the same arithmetic."""
         m = self.model
@@ -383,8 +400,8 @@ class DiTEngine:
             ops.cast_bf16(xo, n, ho)
         T("gemm_cross_q", ops.gemm_bf16, ho, d["wq_c"], d["bq_c"], qo, EPI_BF16, variant=self.gemm_variant)
         T("rmsnorm_rope", ops.rmsnorm_rope, qo, C, 1, d["nq_c"], self.qk_eps)
-        T("attn_cross", ops.attn_fwd, qo, kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], ao, n, ntxt, H, variant=self.attn_variant,
-          q_prescaled=self.q_prescale, kv_padded=True)
+        T("attn_cross", ops.attn_fwd, qo, kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], ao, n, ntxt, H, variant=txt_variant,
+          q_prescaled=self.q_prescale, kv_padded=True, last_key_weight=txt_last_weight)
         if img is not None:
             kc_i, vct_i, n_img = img
             T("attn_cross", ops.attn_fwd, qo, kc_i[:, i * C:(i + 1) * C], vct_i[i * C:(i + 1) * C], ao, n, n_img, H, accumulate=True,
@@ -400,7 +417,9 @@ class DiTEngine:
         """WanAttentionBlock.forward for block i (reference wan23/modules/model.py:272-316, wan/modules/model.py:444-493):
         x [L, C] float; e fp32 [L, 6, C] (per token, 5B) or [1|6, C] (one row, 14B) — the time projection BEFORE the
         block's own modulation is added; rope_cs fp32 [n_rope, 64, 2] (cos, sin) of the first n_rope tokens or None;
-        context [Lc, C] already embedded (the first n_img rows are CLIP image tokens). Returns fp32 [L, C]."""
+        context [Lc, C] already embedded (the first n_img rows are CLIP image tokens). Returns fp32 [L, C].
+        dedup_pad_keys does not reach this seam: an embedded context does not say how many of its rows came from pad rows, so every row is
+        one key here, whatever the option says."""
         self.ensure_packed()
         C = self.model.dim
         L = x.shape[0]
@@ -525,14 +544,18 @@ class DiTEngine:
             if clip_fea is None:
                 raise RuntimeError("clip_fea is required by the i2v model")
             n_img = clip_fea.reshape(-1, clip_fea.shape[-1]).shape[0]
-        ctx = self._buf("ctx", (n_img + m.text_len, C), torch.bfloat16)
+        # text rows of the context: text_len, or the prompt's n rows + one zero row that counts text_len - n times (dedup_pad_keys)
+        n_txt, txt_w = m.text_len, 1.0
+        if self.dedup_pad_keys and context.shape[0] < m.text_len:
+            n_txt, txt_w = context.shape[0] + 1, float(m.text_len - context.shape[0])
+        ctx = self._buf("ctx" if n_txt == m.text_len else f"ctx_{n_txt}", (n_img + n_txt, C), torch.bfloat16)
         ctx_fresh = True
         if self.cache_context:
             # storage address + version counter + shape (views of one tensor share all three); holding the references below
             # keeps those addresses from being handed to another tensor while the entry is live
             key = (context.data_ptr(), context._version, tuple(context.shape),
                    None if clip_fea is None else (clip_fea.data_ptr(), clip_fea._version, tuple(clip_fea.shape)),
-                   self._packed_key)
+                   self._packed_key, self.dedup_pad_keys)
             ctx_fresh = key != self._ctx_key
             self._ctx_key, self._ctx_refs = key, (context, clip_fea)
         else:
@@ -545,13 +568,13 @@ class DiTEngine:
         if self.sp is not None:
             if cache is not None:
                 raise NotImplementedError("cache_sample is not combined with sequence parallelism")
-            return self._forward_sp(xs, L, n_hist, tab.view(nb, R, 6, C), row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid)
+            return self._forward_sp(xs, L, n_hist, tab.view(nb, R, 6, C), row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_w)
         n_trim = n_hist if (self.trim_last_block and cache is None) else 0
-        self._blocks(xs, L, tab.view(nb, R, 6, C), row_idx, R, rope, L, ctx, n_img, ctx_fresh, cache=cache, n_trim=n_trim)
+        self._blocks(xs, L, tab.view(nb, R, 6, C), row_idx, R, rope, L, ctx, n_img, ctx_fresh, cache=cache, n_trim=n_trim, txt_last_weight=txt_w)
         ridx_new = row_idx[n_hist:] if row_idx is not None else None
         return self._head(xs[n_hist:], ridx_new, e, R, grid)
 
-    def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid):
+    def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_last_weight=1.0):
         """Blocks + head on this rank's token chunk (sequence_parallel.py:121-152: chunk after the embeddings, gather
         after the head). The embeddings above were computed for all L tokens on every rank (< 0.1 % of the FLOPs)."""
         sp, C = self.sp, self.model.dim
@@ -569,6 +592,6 @@ class DiTEngine:
             il = self._buf("ridx_sp", (Lp,), torch.int32)
             il[:n].copy_(row_idx[lo:hi])
             il[n:].zero_()
-        self._blocks(xl, Lp, tab, il, R, rl, Lp, ctx, n_img, ctx_fresh, n_keys=L)
+        self._blocks(xl, Lp, tab, il, R, rl, Lp, ctx, n_img, ctx_fresh, n_keys=L, txt_last_weight=txt_last_weight)
         y = sp.gather_rows(self._head_rows(xl, il, e, R))
         return self._unpatchify(y[n_hist:L].contiguous(), grid)

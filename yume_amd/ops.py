@@ -195,11 +195,14 @@ ATTN_Q_PRESCALED = 0x100     # YUME_ATTN_Q_PRESCALED
 ATTN_KV_PADDED = 0x200       # YUME_ATTN_KV_PADDED
 
 
-def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False):
+def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False,
+             last_key_weight=1.0):
     """out[Lq, H*128] = softmax(q k^T * scale) v ; q,k token-major bf16 2-D views, vt K-major [H*128, >=Lk].
     q_prescaled: q already carries scale * log2(e) (`scale` is ignored): out = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j).
     kv_padded: the caller guarantees that k's storage is readable up to ceil(Lk/64)*64 rows and that vt has that many columns with finite
-    values behind column Lk (YUME_ATTN_KV_PADDED): with q_prescaled it opens the persistent kernel (attn_fwd8.hip)."""
+    values behind column Lk (YUME_ATTN_KV_PADDED): with q_prescaled it opens the persistent kernel (attn_fwd8.hip).
+    last_key_weight: key Lk - 1 stands for that many identical keys (yume_attn_fwd_kw; variants 0, 2 and 10 = the short-key kernel, Lk <= 128).
+    The weighted export is called only for a weight other than 1 or variant 10; every other call is the one it always was."""
     lib = _lib.load()
     _dev(q, "q", torch.bfloat16)
     _dev(k, "k", torch.bfloat16)
@@ -235,9 +238,13 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
             ws = _attn_ws.get(wkey)
             if ws is None or ws.numel() < nbytes:
                 ws = _attn_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-    rc = lib.yume_attn_fwd_ws(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0,
-                              variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0), _ptr(ws),
-                              nbytes if ws is not None else 0, _stream())
+    flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
+    if last_key_weight != 1.0 or variant == 10:
+        rc = lib.yume_attn_fwd_kw(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, _ptr(ws),
+                                  nbytes if ws is not None else 0, float(last_key_weight), _stream())
+    else:
+        rc = lib.yume_attn_fwd_ws(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, _ptr(ws),
+                                  nbytes if ws is not None else 0, _stream())
     _lib.check(rc, "yume_attn_fwd")
     return out
 
