@@ -2,7 +2,8 @@
 hipcc must keep nothing of its own there — r3 found it spilling THROUGH a[0:3] when several 128-MFMA loop bodies met at a join — so:
 compile the two translation units to assembly (no GPU) and check, for the one-wave-per-SIMD kernels, that no compiler-generated
 instruction (anything outside ;;#ASMSTART / ;;#ASMEND) touches an AGPR, that nothing spills or uses scratch, and that each steady K loop
-is exactly the gap plan: 128 MFMAs, 32 fragment reads, 16 LDS-DMA pieces, 2 barriers, no memory wait the plan does not own."""
+is exactly the gap plan: 128 MFMAs, 32 fragment reads, 16 LDS-DMA pieces, 2 barriers, no memory wait the plan does not own. The second
+half audits the split-K tail's hand-off between workgroups (publish, poll, acquire, flag reset) along the kernel's control flow."""
 import re
 
 import pytest
@@ -114,3 +115,251 @@ def test_w4_bf16_epilogue_stays_lean():
         if run >= 8 and i + 1 < len(mem) and mem[i + 1] == "global_store_dwordx4":
             best = max(best, run)
     assert best >= 8, "the image -> global pass no longer batches its reads"
+
+
+# ---- the split-K tail's hand-off between workgroups (gemm_w4.hpp, w4_finish_piece) ----------------------------------------------------------
+# Guideline 16's checklist for one flag-guarded hand-off, read off the compiled kernel ALONG ITS CONTROL FLOW (every path, loops and the
+# long-branch trampolines included), not in the order of the lines of the file. Only scalar LOADS are matched for "nothing of the slot goes
+# through the scalar path".
+_W4 = "_ZN7gemm_w414gemm_w4_kernelILi0EE"
+_WAIT0 = re.compile(r"^s_waitcnt\b.*\bvmcnt\(0\)")
+_STORE = re.compile(r"^(global|flat|buffer)_(store|atomic)")
+_FLAG_STORE = re.compile(r"^(global_store_dword\s.*\bsc1\b|global_atomic)")
+_LOAD = re.compile(r"^((global|flat|buffer|scratch)_load|s_(buffer_)?load)")
+_SCALAR_LOAD = re.compile(r"^s_(buffer_)?load")
+_FLAG_LOAD = re.compile(r"^(global|buffer)_load_dword\s.*\bsc1\b")
+_LEAVES = ("v_mfma", "s_endpgm")                  # a walk that gets here has left the hand-off (the next piece's K loop, the kernel's end)
+
+
+def _cfg(body):
+    """(instructions, successors) of a kernel body: labels resolved, `s_getpc / s_add (.LBB - .Lpost_getpc) / s_setpc` trampolines followed"""
+    ins, labels = [], {}
+    for line in body:
+        t = line.split(";")[0].strip()
+        m = re.match(r"^(\.L\w+):", t)
+        if m:
+            labels[m.group(1)] = len(ins)
+        elif t and not t.startswith(".") and not t.endswith(":"):
+            ins.append(t)
+    succ = []
+    for i, x in enumerate(ins):
+        op = x.split()[0]
+        assert op not in ("s_swappc_b64", "s_call_b64"), "a call inside the kernel: the walk below does not follow it"
+        if op == "s_endpgm":
+            succ.append([])
+        elif op == "s_branch":
+            succ.append([labels[x.split()[1]]])
+        elif op.startswith("s_cbranch"):
+            succ.append([labels[x.split()[1]], i + 1])
+        elif op == "s_setpc_b64":
+            tgt = [re.search(r"\((\.LBB\d+_\d+)-\.Lpost_getpc", y) for y in ins[max(0, i - 4):i]]
+            tgt = [m.group(1) for m in tgt if m]
+            assert tgt, "s_setpc_b64 whose target is not a label"
+            succ.append([labels[tgt[0]]])
+        else:
+            succ.append([i + 1])
+    return ins, succ
+
+
+def _walk(starts, succ, visit):
+    """depth-first over (instruction, state): visit(i, state) -> the state its successors are entered with, or None to stop that path"""
+    seen, todo = set(), [(i, s) for i, s in starts]
+    while todo:
+        i, s = todo.pop()
+        if (i, s) in seen:
+            continue
+        seen.add((i, s))
+        ns = visit(i, s)
+        if ns is not None:
+            todo.extend((j, ns) for j in succ[i])
+
+
+def _w4_cfg():
+    body, _ = _kernel_body(_asm("gemm_bf16.hip"), _W4)
+    return _cfg(body)
+
+
+def _blocks(ins, succ):
+    """basic-block number of every instruction"""
+    leader = {0}
+    for i, ss in enumerate(succ):
+        if ss != [i + 1]:
+            leader.update(ss)
+            leader.add(i + 1)
+    blk, b = [], -1
+    for i in range(len(ins)):
+        b += i in leader
+        blk.append(b)
+    return blk
+
+
+def test_w4_handoff_publish_drains_every_wave_before_the_flag():
+    """64 write-through payload stores per operand order in one basic block; on every path from the last of them the wave waits for
+    vmcnt(0), THEN reaches the workgroup's barrier, and the next store behind that is the flag's (an sc1 dword store or an atomic)."""
+    ins, succ = _w4_cfg()
+    pay = [i for i, x in enumerate(ins) if x.startswith("global_store_dwordx4") and re.search(r"\bsc1\b", x)]
+    assert len(pay) == 128, len(pay)
+    blk = _blocks(ins, succ)
+    groups = {}
+    for i in pay:
+        groups.setdefault(blk[i], []).append(i)
+    assert sorted(len(g) for g in groups.values()) == [64, 64], "the payload stores of an operand order no longer sit in one basic block"
+    for g in groups.values():
+        flags = []
+
+        def visit(i, s):
+            x = ins[i]
+            if i == g[-1]:
+                return 0
+            if x.startswith(_LEAVES) or " lds" in x or "_load_lds" in x:
+                return None
+            if _WAIT0.match(x):
+                return max(s, 1)
+            if x.startswith("s_barrier"):
+                assert s >= 1, "a publishing wave reaches the barrier with payload stores in flight"
+                return 2
+            if _STORE.match(x):
+                assert _FLAG_STORE.match(x), f"a store other than the flag's follows the payload: {x}"
+                assert s == 2, f"the flag store is not behind vmcnt(0) + barrier: {x}"
+                flags.append(i)
+                return None
+            return s
+        _walk([(g[-1], 0)], succ, visit)
+        assert flags, "no flag store behind the payload"
+
+
+def _spins(ins, succ):
+    """the innermost loops that sleep: instructions on a cycle through an s_sleep that crosses no barrier / invalidate / MFMA"""
+    pred = [[] for _ in ins]
+    for i, ss in enumerate(succ):
+        for j in ss:
+            pred[j].append(i)
+    cut = lambda x: x.startswith(("s_barrier", "buffer_inv") + _LEAVES)      # noqa: E731
+    out = []
+    for s0 in (i for i, x in enumerate(ins) if x.startswith("s_sleep")):
+        def reach(edges):
+            seen, todo = set(), [s0]
+            while todo:
+                i = todo.pop()
+                for j in edges[i]:
+                    if j not in seen and not cut(ins[j]):
+                        seen.add(j)
+                        todo.append(j)
+            return seen
+        scc = frozenset(reach(succ) & reach(pred))
+        assert s0 in scc, "an s_sleep outside a loop"
+        if scc not in out:
+            out.append(scc)
+    return out
+
+
+def test_w4_handoff_poll_is_relaxed_sleeps_and_gives_up_into_the_error_word():
+    ins, succ = _w4_cfg()
+    spins = _spins(ins, succ)
+    assert len(spins) == 2, len(spins)                                    # one per operand order
+    for scc in spins:
+        loads = [ins[i] for i in scc if _LOAD.match(ins[i])]
+        assert loads and all(_FLAG_LOAD.match(x) for x in loads), loads       # the flag, past the L1, and nothing else
+        assert not [ins[i] for i in scc if _STORE.match(ins[i])]
+        assert not [ins[i] for i in scc if ins[i].startswith("buffer_inv")], "an acquire per poll"
+        assert [ins[i] for i in scc if re.match(r"^[sv]_(add|sub|addk)\w*\s", ins[i])], "no spin counter inside the loop: the spin is not bounded"
+        exits = {j for i in scc for j in succ[i] if j not in scc}
+        reached = set()                                                      # states (0: nothing stored, 1: the error word) at the acquire
+
+        def visit(i, s):
+            x = ins[i]
+            if x.startswith("buffer_inv"):
+                assert re.search(r"\bsc1\b", x), x
+                reached.add(s)
+                return None
+            assert not x.startswith(("s_barrier",) + _LEAVES), "a path leaves the poll without the acquire"
+            assert not _LOAD.match(x), f"a load between the poll's exit and the acquire: {x}"
+            if _STORE.match(x):
+                assert _FLAG_STORE.match(x), x
+                return 1
+            return s
+        _walk([(j, 0) for j in exits], succ, visit)
+        assert reached == {0, 1}, "the poll needs its normal exit and a give-up exit that stores to the error word"
+
+
+def test_w4_handoff_acquire_is_waited_for_before_the_barrier():
+    """fence -> that lane's s_waitcnt vmcnt(0) -> barrier: s_barrier waits for no counter, so without the wait the other waves may gather the
+    slot before the L1 invalidate has landed. And nothing loads between the invalidate and that barrier."""
+    ins, succ = _w4_cfg()
+    invs = [i for i, x in enumerate(ins) if x.startswith("buffer_inv")]
+    assert len(invs) == 2 and all(re.search(r"\bsc1\b", ins[i]) for i in invs), [ins[i] for i in invs]
+    for inv in invs:
+        barriers = []
+
+        def visit(i, s):
+            x = ins[i]
+            if i == inv:
+                return 0
+            assert not x.startswith(_LEAVES), "no barrier behind the acquire"
+            assert not _LOAD.match(x), f"a load between the acquire and the barrier: {x}"
+            if _WAIT0.match(x):
+                return 1
+            if x.startswith("s_barrier"):
+                assert s == 1, "buffer_inv sc1 reaches s_barrier without an s_waitcnt vmcnt(0) in between"
+                barriers.append(i)
+                return None
+            return s
+        _walk([(inv, 0)], succ, visit)
+        assert barriers
+
+
+def test_w4_handoff_flag_reset_is_behind_the_gathers_barrier():
+    """The gather: 64 plain 16-byte vector loads per operand order between the acquire's barrier and the next one, none through the scalar
+    path; every one of them has landed (vmcnt(0)) before that next barrier, no store is reachable from one without crossing it, and the
+    flag's reset (an sc1 dword store) follows it before anything else is loaded."""
+    ins, succ = _w4_cfg()
+    for inv in (i for i, x in enumerate(ins) if x.startswith("buffer_inv")):
+        gather = set()
+
+        def visit(i, s):
+            x = ins[i]
+            if i == inv:
+                return 0
+            if x.startswith(("buffer_inv",) + _LEAVES):
+                return None
+            assert not _SCALAR_LOAD.match(x), f"a scalar load inside the hand-off: {x}"
+            if x.startswith("s_barrier"):
+                return None if s == 1 else 1
+            if _LOAD.match(x):
+                assert s == 1 and re.match(r"^global_load_dwordx4\s", x) and " lds" not in x, \
+                    f"between the acquire's barrier and the next one only the gather's 16-byte vector loads may load: {x}"
+                gather.add(i)
+            return s
+        _walk([(inv, 0)], succ, visit)
+        assert len(gather) == 64, len(gather)
+        after = set()
+        for g in gather:
+            def visit2(i, s):
+                x = ins[i]
+                if i == g:
+                    return 0
+                assert not x.startswith(("buffer_inv",) + _LEAVES)
+                assert not _STORE.match(x), f"a store reachable from a gather load without a barrier: {x}"
+                if _WAIT0.match(x):
+                    return 1
+                if x.startswith("s_barrier"):
+                    assert s == 1, "a gather load may be in flight at the barrier in front of the flag's reset"
+                    after.add(i)
+                    return None
+                return s
+            _walk([(g, 0)], succ, visit2)
+        assert len(after) == 1, after
+        first_stores = []
+
+        def visit3(i, s):
+            x = ins[i]
+            if s == 0:
+                return 1                                                     # (the barrier itself)
+            if x.startswith(("s_barrier", "buffer_inv") + _LEAVES) or _LOAD.match(x):
+                return None
+            if _STORE.match(x):
+                first_stores.append(x)
+                return None
+            return s
+        _walk([(next(iter(after)), 0)], succ, visit3)
+        assert [x for x in first_stores if _FLAG_STORE.match(x)], f"no flag reset behind the gather's barrier: {first_stores}"

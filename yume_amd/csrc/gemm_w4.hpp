@@ -573,7 +573,9 @@ __device__ __forceinline__ void w4_mainloop(const Problem& p, const PlainA& al, 
 //   its operands at HBM rate, 2.8 us per K tile instead of 1.4 — profiles/r6_gemm_streamk_contiguous_first_run.log. Here every workgroup of a
 //   group walks the SAME K range in step with its neighbours, as the whole-tile rounds do.)
 //   * a tail slice PUBLISHES its 256 x 256 fp32 partial (write-through `sc1` stores into the caller's scratch, every wave drains, one lane
-//     raises the slice's flag); the head FINISHES the tile: it polls the flags of the tile's tail slices, one agent-scope acquire each, adds
+//     raises the slice's flag); the head FINISHES the tile: one lane polls the flag of each of the tile's tail slices, then agent-scope acquire
+//     fence -> that lane's `s_waitcnt vmcnt(0)` -> workgroup barrier -> every wave's plain loads of the slot (Guideline 16: the barrier waits
+//     for no counter, the wait holds it for the L1 invalidate; tests/test_gemm_w4_isa.py audits the order in the assembly); it adds
 //     the partials IN SLICE ORDER into its accumulators (a fixed summation order whatever the timing: results are run-to-run identical) and
 //     runs the tile's epilogue. Flags return to zero behind their reader (a launch leaves the scratch as it found it: no memset, capturable).
 // Every spin is bounded (a timeout raises the scratch's error word instead of hanging). Placement-independent: every workgroup of the tail
@@ -641,6 +643,7 @@ __device__ __forceinline__ void w4_finish_piece(const Problem& p, const Epilogue
                     }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the barrier waits for no counter: hold it for the L1 invalidate
             }
             __syncthreads();
             sk_gather_tiles<0, 64>(slots + (int64_t)q * SK_SLOT_BYTES, lane_off);
