@@ -174,8 +174,8 @@ int yume_rmsnorm_rows_periodic(void* buf, int64_t ld, int64_t T, int64_t C, cons
  * O: bf16 token-major (ldo). accumulate != 0: O += result (the 14B image cross-attention sum,
  *    wan/modules/model.py:379-387) using the fp32 accumulator before rounding.
  * variant: 0 = automatic (Lk >= 1536 and Lq >= 256: the one-wave-per-SIMD kernel, 256 queries per workgroup; otherwise
- *    the 4-wave LDS-DMA kernel), 1 = 4-wave register-staged kernel, 2 = 4-wave LDS-DMA kernel, 4 = 8-wave ping-pong
- *    kernel, 7 = one-wave-per-SIMD kernel (attn_fwd7.hip), 8 = its persistent form (attn_fwd8.hip; needs the two flags below),
+ *    the 4-wave LDS-DMA kernel), 1 = 4-wave register-staged kernel (attn_fwd_v1.hpp), 2 = 4-wave LDS-DMA kernel (attn_fwd_v2.hpp),
+ *    4 = 8-wave ping-pong kernel (attn_fwd_v4.hpp), 7 = one-wave-per-SIMD kernel (attn_fwd7.hip), 8 = its persistent form (attn_fwd8.hip; needs the two flags below),
  *    9 = the short-key kernel with K and V^T resident in registers (attn_cross_rk.hpp, r6: 448 < Lk <= 512, Lq >= 1024, ldvt >= 512, and
  *    for Lk < 512 YUME_ATTN_KV_PADDED — the 512-token text cross-attention; measured slower than the 4-wave kernel as built, so variant 0
  *    takes it only with env YUME_ATTN_RK=1). All compute the same function (tests compare them).

@@ -112,6 +112,15 @@ def test_attention_plan_workspace_sizes():
     assert lib.yume_attn_workspace_bytes(8192, 9460, H) == 0          # 96 blocks per XCD: whole rounds, nothing to cut
     assert lib.yume_attn_workspace_bytes(9460, 512, H) == 0           # cross-attention: other kernel
     assert lib.yume_attn_workspace_bytes(100, 9460, H) == 0
+    # the larger of the two split plans (attn_fwd7 / attn_fwd8 cost models), pinned per shape: what the library answered before the
+    # plans were written once (attn_plan.hpp)
+    pinned = [
+        (9460, 9460, 24, 31_649_280), (27810, 27810, 40, 13_478_400), (12545, 12545, 24, 89_506_560), (11000, 11000, 24, 12_380_160),
+        (10240, 10240, 24, 102_236_160), (3520, 3520, 24, 35_942_400), (256, 1536, 24, 9_584_640), (1182, 9460, 24, 29_502_720),
+        (9460, 9460, 3, 7_912_320), (4730, 9460, 24, 0), (27810, 27810, 5, 0), (9460, 576, 24, 0), (256, 512, 24, 0),
+    ]
+    for Lq, Lk, heads, want in pinned:
+        assert lib.yume_attn_workspace_bytes(Lq, Lk, heads) == want, (Lq, Lk, heads)
 
 
 def test_level0_patch_grid_refuses_odd_sizes():

@@ -1,4 +1,4 @@
-// attn_args.hpp — launch arguments shared by the attention kernels (attn_fwd.hip, attn_fwd7.hip).
+// attn_args.hpp — launch arguments shared by the attention kernels (attn_fwd.hip and its kernel headers, attn_fwd7.hip, attn_fwd8.hip).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -14,12 +14,13 @@ struct AttnArgs {
     int accumulate;
     int nqb;           // query blocks per head (of the rows [q_lo, Lq) this launch covers)
     int q_lo;          // first query row of this launch
-    // key-range split (gridDim.y = splits > 1, v2 kernel only): split s walks key tiles [nt*s/splits, nt*(s+1)/splits) and writes
-    // its UNNORMALISED O (fp32) + running max + row sum here; attn_combine_kernel merges the splits
-    float* part_o;     // [splits, Lq - q_lo, H*128]
-    float* part_ml;    // [splits, Lq - q_lo, H, 2]
-    // v7 kernel only: query blocks >= tail_qb are cut into `splits` key ranges inside the same launch (their pieces are dispatched
-    // after the whole blocks and fill the partial last round of workgroups); partials as above with rows = Lq - (q_lo + 256*tail_qb)
+    // key-range split (the v7 and v8 kernels, planned by attn_plan.hpp): query blocks >= tail_qb are cut into `splits` key ranges inside the
+    // same launch (their pieces come after the whole blocks and fill the partial last round of workgroups). Piece s walks key tiles
+    // [nt*s/splits, nt*(s+1)/splits) and writes its UNNORMALISED O (fp32) + running max + row sum here; attn_combine_kernel (attn_combine.hpp)
+    // merges the pieces. rows = Lq - (q_lo + 256*tail_qb). No launch splits the other kernels: they see tail_qb == nqb, splits == 1 and
+    // never touch part_o / part_ml (attn_fwd_kernel_v2 still carries a gridDim.y split that no launch uses).
+    float* part_o;     // [splits, rows, H*128]
+    float* part_ml;    // [splits, rows, H, 2]
     int tail_qb, splits;
     // yume_attn_fwd_kw: the LAST key (Lk - 1) counts last_w times (its exponential is multiplied by it); exactly 1 on every other call.
     // Read by attn_fwd_kernel_v2<true> and attn_short.hpp only
