@@ -233,6 +233,24 @@ int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
 int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
                      void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale,
                      int accumulate, int variant, void* workspace, int64_t workspace_bytes, float last_key_weight, void* stream);
+/* SEGMENTED form (r9): ONE launch serves nseg (1 .. 8) independent attention problems that share Q's and O's buffers and every shape but the
+ * key count. Segment s owns the query rows [s * seg_pitch, s * seg_pitch + Lq_seg) of Q and O (seg_pitch >= Lq_seg, in rows; the rows of the
+ * gap are neither read nor written) and attends over its own K[s] / Vt[s] (Lk[s] keys, key Lk[s] - 1 counting last_key_weight[s] times).
+ * replaces: the text cross-attention of the two forwards of a classifier-free-guidance pair (fastvideo/sample/sample.py:774-779 calls the
+ *           model twice with everything equal but `context`), run as one pass over the stacked rows of both (DiTEngine.forward_pair).
+ * K, Vt: HOST arrays of nseg device pointers; Lk: host array of nseg key counts; last_key_weight: host array of nseg weights, or NULL = all 1.
+ *    The arrays are read during the call and travel to the kernel by value (a captured graph needs no device memory for them). No workspace.
+ * ldq, ldk, ldvt (>= every Lk[s]), ldo, H, scale, accumulate, YUME_ATTN_Q_PRESCALED / YUME_ATTN_KV_PADDED: as for yume_attn_fwd_kw, common
+ *    to all segments. Checks (YUME_EINVAL by name): nseg in [1, 8], seg_pitch >= Lq_seg, every pointer non-NULL and 16-byte aligned, every
+ *    Lk[s] >= 1, every weight finite and in [1, 2^20].
+ * variant 0  = the segmented short-key kernel when EVERY Lk[s] <= 128 (and ldo % 8 == 0, 16-byte aligned O, env YUME_ATTN_SHORT not 0),
+ *              otherwise the segmented 4-wave LDS-DMA kernel;
+ * variant 10 = insists on the short-key kernel (YUME_EINVAL when some Lk[s] > 128 or the alignment fails); variant 2 on the 4-wave kernel;
+ * any other variant: YUME_EUNSUP (the message names it).
+ * nseg == 1 is yume_attn_fwd_kw(Q, .., K[0], .., Vt[0], .., Lq_seg, Lk[0], .., last_key_weight[0]): same kernel choice, same bits. */
+int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* K, int64_t ldk, const void* const* Vt, int64_t ldvt,
+                      void* O, int64_t ldo, int64_t nseg, int64_t Lq_seg, int64_t seg_pitch, const int64_t* Lk, int64_t H,
+                      float scale, int accumulate, int variant, const float* last_key_weight, void* stream);
 
 /* ---- small-M fp32 linear (time embedding MLP) ---------------------------------------------
  * replaces: wan23/modules/model.py:459-461,803-812 (time_embedding, time_projection under

@@ -36,6 +36,7 @@ SIGNATURES = {
     "yume_attn_workspace_bytes": [_L, _L, _L],
     "yume_attn_fwd_ws": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _P, _L, _P],
     "yume_attn_fwd_kw": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _P, _L, _F, _P],
+    "yume_attn_fwd_seg": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _F, _I, _I, _P, _P],
     "yume_linear_smallm_f32": [_P, _L, _L, _P, _I, _P, _L, _I, _I, _P, _P, _P],
     "yume_sinusoidal_embed": [_P, _P, _L, _L, _P, _P],
     "yume_modulation_table": [_P, _P, _L, _L, _L, _P, _P],

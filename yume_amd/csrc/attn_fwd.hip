@@ -1,5 +1,6 @@
 // attn_fwd.hip — exact-softmax attention forward for head_dim 128, bf16 in / fp32 accumulate / bf16 out (gfx950): the C-ABI entry points
-// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_workspace_bytes) and the dispatcher behind them: validate -> choose -> launch.
+// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_fwd_seg, yume_attn_workspace_bytes) and the dispatcher behind them:
+// validate -> choose -> launch.
 //
 // Seven kernels compute the same function (choose() picks; the tests compare them). Each lives in a file of its own with its design comment:
 //   attn_fwd_kernel_v8    attn_fwd8.hip       persistent workgroups over one continuous K / V^T stream (self-attention; needs pre-scaled Q,
@@ -11,6 +12,7 @@
 //   attn_fwd_kernel       attn_fwd_v1.hpp     as v2 with register-staged tiles (the first version; kept as an independent cross-check)
 //   attn_cross_rk_kernel  attn_cross_rk.hpp   448 < Lk <= 512: K and V^T resident in a workgroup's registers
 //   attn_short_kernel     attn_short.hpp      Lk <= 128: a head's K and V^T resident in one wave's registers (takes the weighted last key)
+// yume_attn_fwd_seg (several independent segments in one launch) has the segmented forms of the last two of its own: attn_seg.hpp.
 // and attn_combine_kernel (attn_combine.hpp) merges the key-range pieces of a split v7 / v8 launch, planned by attn_plan.hpp.
 // The transposed formulation and the tile layouts the kernels share: attn_tile.hpp.
 #include "common.hpp"
@@ -23,6 +25,7 @@
 #include "attn_combine.hpp"
 #include "attn_cross_rk.hpp"
 #include "attn_short.hpp"
+#include "attn_seg.hpp"
 #include <math.h>
 
 static_assert(attn_plan::QBLOCK == QB4 && attn_plan::KTILE == KT && attn_plan::HDIM == D, "attn_plan.hpp restates the tile constants");
@@ -229,4 +232,55 @@ extern "C" int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64
     YUME_REQUIRE(isfinite(last_key_weight) && last_key_weight >= 1.0f && last_key_weight <= 1048576.0f,
                  "attn_fwd_kw: last_key_weight=%g must be finite and in [1, 2^20]", (double)last_key_weight);
     return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, last_key_weight, stream);
+}
+
+// Segmented cross-attention (attn_seg.hpp): nseg independent problems of Lq_seg queries each, seg_pitch rows apart in Q and O, every one with
+// its own K / V^T / Lk / last-key weight (host arrays, copied into the kernel arguments). nseg == 1 IS yume_attn_fwd_kw.
+extern "C" int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* K, int64_t ldk, const void* const* Vt, int64_t ldvt,
+                                 void* O, int64_t ldo, int64_t nseg, int64_t Lq_seg, int64_t seg_pitch, const int64_t* Lk, int64_t H,
+                                 float scale, int accumulate, int variant, const float* last_key_weight, void* stream) {
+    YUME_REQUIRE(nseg >= 1 && nseg <= ATTN_SEG_MAX, "attn_fwd_seg: nseg=%lld must be in [1, %d]", (long long)nseg, ATTN_SEG_MAX);
+    YUME_REQUIRE(Q && K && Vt && O && Lk, "attn_fwd_seg: NULL pointer");
+    YUME_REQUIRE(Lq_seg > 0 && H > 0, "attn_fwd_seg: empty problem Lq_seg=%lld H=%lld", (long long)Lq_seg, (long long)H);
+    YUME_REQUIRE(seg_pitch >= Lq_seg, "attn_fwd_seg: seg_pitch=%lld must be >= Lq_seg=%lld", (long long)seg_pitch, (long long)Lq_seg);
+    YUME_REQUIRE(Lq_seg < (1ll << 30) && seg_pitch * nseg < (1ll << 30) && H < 65536, "attn_fwd_seg: dimension too large");
+    YUME_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldvt % 8) == 0 && (ldo % 4) == 0, "attn_fwd_seg: ldq/ldk/ldvt must be multiples of 8, ldo of 4");
+    YUME_REQUIRE(ldk < (1ll << 24) && ldvt < (1ll << 24) && ldvt >= 8, "attn_fwd_seg: ldk / ldvt out of range for 32-bit tile offsets");
+    YUME_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)O % 8) == 0, "attn_fwd_seg: pointer alignment");
+    AttnSegArgs a{};
+    int64_t lk_max = 0;
+    for (int s = 0; s < (int)nseg; ++s) {
+        YUME_REQUIRE(K[s] && Vt[s], "attn_fwd_seg: NULL K / Vt pointer of segment %d", s);
+        YUME_REQUIRE(((uintptr_t)K[s] % 16) == 0 && ((uintptr_t)Vt[s] % 16) == 0, "attn_fwd_seg: pointer alignment of segment %d", s);
+        YUME_REQUIRE(Lk[s] > 0 && Lk[s] < (1ll << 30), "attn_fwd_seg: Lk[%d]=%lld must be in [1, 2^30)", s, (long long)Lk[s]);
+        YUME_REQUIRE(ldvt >= Lk[s], "attn_fwd_seg: ldvt=%lld must be >= Lk[%d]=%lld", (long long)ldvt, s, (long long)Lk[s]);
+        const float w = last_key_weight ? last_key_weight[s] : 1.0f;
+        YUME_REQUIRE(isfinite(w) && w >= 1.0f && w <= 1048576.0f, "attn_fwd_seg: last_key_weight[%d]=%g must be finite and in [1, 2^20]", s, (double)w);
+        a.K[s] = (const unsigned short*)K[s];
+        a.Vt[s] = (const unsigned short*)Vt[s];
+        a.Lk[s] = (int)Lk[s];
+        a.last_w[s] = w;
+        lk_max = Lk[s] > lk_max ? Lk[s] : lk_max;
+    }
+    const int flags = variant & (YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 2 && v != 10) {
+        yume_set_error("attn_fwd_seg: variant %d has no segmented kernel (variants 0, 2 and 10 do)", v);
+        return YUME_EUNSUP;
+    }
+    if (v == 10) YUME_REQUIRE(lk_max <= attn_short::LKMAX, "attn_fwd_seg: variant 10 (short-key kernel) needs every Lk <= 128, got %lld", (long long)lk_max);
+    if (nseg == 1)      // one segment is the plain weighted call: same kernel choice, same bits
+        return yume_attn_fwd_kw(Q, ldq, K[0], ldk, Vt[0], ldvt, O, ldo, Lq_seg, Lk[0], H, scale, accumulate, v | flags, nullptr, 0, a.last_w[0], stream);
+    a.Q = (const unsigned short*)Q; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt;
+    a.O = (unsigned short*)O; a.ldo = ldo;
+    a.nseg = (int)nseg; a.Lq_seg = (int)Lq_seg; a.seg_pitch = (int)seg_pitch; a.H = (int)H;
+    a.scale_log2 = (flags & YUME_ATTN_Q_PRESCALED) ? 1.0f : scale * 1.4426950408889634f;
+    a.accumulate = accumulate;
+    hipStream_t st = (hipStream_t)stream;
+    const bool fits = attn_seg::short_fits(a);
+    if (v == 10) YUME_REQUIRE(fits, "attn_fwd_seg: variant 10 (short-key kernel) needs ldo %% 8 == 0 and a 16-byte aligned O");
+    if (v == 10 || (v == 0 && fits && attn_short_auto())) attn_seg::launch_short(a, cu_count(), st);
+    else attn_seg::launch_v2(a, st);
+    YUME_CHECK_LAUNCH("attn_fwd_seg");
+    return YUME_OK;
 }

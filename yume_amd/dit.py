@@ -70,6 +70,8 @@ class DiTEngine:
         self.sp = None
         self._ctx_key = None
         self._ctx_refs = None
+        self._pair_ctx_key = None          # forward_pair's own conditioning cache (its K / V^T live in buffers of their own)
+        self._pair_ctx_refs = None
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -279,15 +281,16 @@ class DiTEngine:
         ops.gemm_bf16(h, w3, b3, y, EPI_F32, variant=self.gemm_variant)
         ops.adaln_modulate(y, l4w, l4b, 0, None, False, out_rows, 0, eps=1e-5)
 
-    def _cross_kv(self, tag, ctx_rows, nk, wkv, bkv, nk_w, fresh):
+    def _cross_kv(self, tag, ctx_rows, nk, wkv, bkv, nk_w, fresh, cols=None):
         """K (RMS-normalised) and K-major V^T of all blocks for one conditioning stream: kc [nk, nb*C], vct [nb*C, nk8].
-        Recomputed only when `fresh` (always, unless cache_context found the same conditioning tensors)."""
+        Recomputed only when `fresh` (always, unless cache_context found the same conditioning tensors).
+        cols: columns of vct where the caller needs more than nk's own whole tiles (forward_pair: both legs' V^T with one row stride)."""
         C, nb = self.model.dim, len(self.P["blocks"])
         # rows / columns up to a whole number of 64-key tiles exist and hold zeros: the attention kernels may fetch the ragged last key tile
         # like any other (YUME_ATTN_KV_PADDED); the GEMM below writes nk rows / columns only
         nk64 = _round_up(nk, 64)
         kc = self._buf(f"kc_{tag}_{nk}", (nk64, nb * C), torch.bfloat16, zero=True)[:nk]
-        vct = self._buf(f"vct_{tag}_{nk}", (nb * C, nk64), torch.bfloat16, zero=True)
+        vct = self._buf(f"vct_{tag}_{nk}", (nb * C, nk64 if cols is None else cols), torch.bfloat16, zero=True)
         if fresh:
             ops.gemm_bf16(ctx_rows, wkv, bkv, kc, EPI_BF16_SPLITT, out_t=vct, n_split=nb * C, variant=self.gemm_variant)
             ops.rmsnorm_rows_periodic(kc.view(nk * nb, C), C, nk_w, self.qk_eps)
@@ -466,11 +469,10 @@ class DiTEngine:
         return y
 
     # ------------------------------------------------------------------ one sample forward
-    @torch.no_grad()
-    def forward_one(self, u, t, context, clip_fea=None, packed=True, lfz=8, n_sel=None, cache=None):
-        """u [Cin, F, H, W] (fp32|bf16, x and y already concatenated); t tensor; context [Ltxt, text_dim].
-        Returns fp32 [Cout, F', H, W]."""
-        self.ensure_packed()
+    def _prologue(self, u, t, packed, lfz, n_sel, pair=False):
+        """what a forward does before the conditioning enters: the per-clip tables, the timestep rows, the patch embedding into the residual
+        stream and the modulation table. Returns (xs, L, n_hist, grid, rope, R, row_idx, e, tab). pair: the residual stream is forward_pair's
+        stacked buffer (the embedding fills its first L rows)."""
         m = self.model
         C, D = m.dim, m.dim // m.num_heads
         if D != 128:
@@ -530,7 +532,7 @@ class DiTEngine:
             row_idx = inv.to(torch.int32).contiguous()
 
         # --- embeddings
-        xs = self._buf("xs", (L, C), torch.float32)
+        xs = self._buf("xs_p", (_round_up(L, 64) + L, C), torch.float32) if pair else self._buf("xs", (L, C), torch.float32)
         off = 0
         for g in groups:
             self._embed_group(u, g, xs[off:off + g.ntok])
@@ -539,6 +541,17 @@ class DiTEngine:
         nb = len(self.P["blocks"])
         tab = self._buf("tab", (nb, R, 6 * C), torch.float32)
         ops.modulation_table(self.P["mod_all"], e0, tab)
+        return xs, L, n_hist, grid, rope, R, row_idx, e, tab
+
+    @torch.no_grad()
+    def forward_one(self, u, t, context, clip_fea=None, packed=True, lfz=8, n_sel=None, cache=None):
+        """u [Cin, F, H, W] (fp32|bf16, x and y already concatenated); t tensor; context [Ltxt, text_dim].
+        Returns fp32 [Cout, F', H, W]."""
+        self.ensure_packed()
+        m = self.model
+        C = m.dim
+        xs, L, n_hist, grid, rope, R, row_idx, e, tab = self._prologue(u, t, packed, lfz, n_sel)
+        nb = len(self.P["blocks"])
         n_img = 0
         if self.family == "wan":
             if clip_fea is None:
@@ -573,6 +586,131 @@ class DiTEngine:
         self._blocks(xs, L, tab.view(nb, R, 6, C), row_idx, R, rope, L, ctx, n_img, ctx_fresh, cache=cache, n_trim=n_trim, txt_last_weight=txt_w)
         ridx_new = row_idx[n_hist:] if row_idx is not None else None
         return self._head(xs[n_hist:], ridx_new, e, R, grid)
+
+    # ------------------------------------------------------------------ a guided (classifier-free guidance) pair in one pass
+    @torch.no_grad()
+    def forward_pair(self, u, t, context, context_null, clip_fea=None, packed=True, lfz=8, n_sel=None):
+        """The two forwards of a classifier-free-guidance step — same u, t and clip_fea, two prompts (fastvideo/sample/sample.py:774-779) — as
+        ONE pass over the stacked rows of both legs. Returns (cond, uncond), each what forward_one returns for that context (fp32).
+
+        Everything in front of block 0's first cross-attention does not depend on the prompt and runs once on L rows: patch embedding, time
+        rows, modulation table, the CLIP image context with its K / V^T, and block 0's adaLN -> QKV -> RMSNorm+RoPE -> self-attention ->
+        o projection. The residual stream is then copied to leg 1, `pitch` = ceil(L / 64) * 64 rows further on: the QKV GEMM writes V^T
+        columns by stacked row and the self-attention kernels fetch K rows / V^T columns up to a whole 64-key tile, so leg 1 must start on
+        a tile. The pitch - L rows between the legs are a token of their own (they start at zero, stay finite, are never keys and never
+        returned). From there every adaLN, cast, GEMM and norm launch runs once over the pitch + L stacked rows with the row selector and
+        RoPE table repeated per leg; self-attention is one launch per leg on row / column views; the CLIP image cross-attention one
+        accumulating launch over all stacked queries (both legs share its keys); the text cross-attention ONE segmented launch
+        (ops.attn_fwd_seg), each leg over its own K / V^T — with dedup_pad_keys its own n + 1 keys and last-key weight.
+
+        cache_context keys on both contexts (and keeps its own K / V^T buffers: forward_one's cache is not disturbed). trim_last_block is
+        ignored here: the last block runs on every row. Sequence parallelism and the block-residual cache are not implemented for the pair."""
+        if self.sp is not None:
+            raise NotImplementedError("forward_pair is not implemented under sequence parallelism (enable_sequence_parallel)")
+        self.ensure_packed()
+        m = self.model
+        C, H, nb = m.dim, m.num_heads, len(self.P["blocks"])
+        xs, L, n_hist, grid, rope, R, row_idx, e, tab = self._prologue(u, t, packed, lfz, n_sel, pair=True)
+        pitch = _round_up(L, 64)
+        M = pitch + L                                                   # stacked rows: leg 0, the gap, leg 1
+        n_img = 0
+        if self.family == "wan":
+            if clip_fea is None:
+                raise RuntimeError("clip_fea is required by the i2v model")
+            n_img = clip_fea.reshape(-1, clip_fea.shape[-1]).shape[0]
+        legs = []
+        for c in (context, context_null):
+            n_txt, txt_w = m.text_len, 1.0
+            if self.dedup_pad_keys and c.shape[0] < m.text_len:
+                n_txt, txt_w = c.shape[0] + 1, float(m.text_len - c.shape[0])
+            legs.append((c, n_txt, txt_w))
+        ctx_fresh = True
+        if self.cache_context:
+            key = tuple((c.data_ptr(), c._version, tuple(c.shape)) for c in (context, context_null)) + (
+                None if clip_fea is None else (clip_fea.data_ptr(), clip_fea._version, tuple(clip_fea.shape)), self._packed_key, self.dedup_pad_keys)
+            ctx_fresh = key != self._pair_ctx_key
+            self._pair_ctx_key, self._pair_ctx_refs = key, (context, context_null, clip_fea)
+        else:
+            self._pair_ctx_key = None
+        cols = _round_up(max(n for _, n, _ in legs), 64)               # one V^T row stride for both legs
+        kv_t = []
+        for s, (c, n_txt, _) in enumerate(legs):
+            ctx = self._buf(f"ctx_p{s}_{n_txt}", (n_txt, C), torch.bfloat16)
+            if ctx_fresh:
+                self._text_ctx(c, ctx)
+            kv_t.append(self._cross_kv(f"p{s}c{cols}", ctx, n_txt, self.P["wkv_c"], self.P["bkv_c"], self.P["nk_c"], ctx_fresh, cols=cols))
+        kv_i = None
+        if n_img:
+            ctx = self._buf("ctx_pi", (n_img, C), torch.bfloat16)
+            if ctx_fresh:
+                self._img_ctx(clip_fea, ctx)
+            kv_i = self._cross_kv("pi", ctx, n_img, self.P["wkv_i"], self.P["bkv_i"], self.P["nk_i"], ctx_fresh)
+
+        # --- stacked tables: the row selector and the RoPE rows once per leg (the gap: row 0 of the table, a zero rotation)
+        ridx2 = None
+        if row_idx is not None:
+            ridx2 = self._buf("ridx_p", (M,), torch.int32, zero=True)
+            ridx2[:L].copy_(row_idx)
+            ridx2[pitch:].copy_(row_idx)
+        rope2 = self._buf("rope_p", (M,) + tuple(rope.shape[1:]), torch.float32, zero=True)
+        rope2[:L].copy_(rope)
+        rope2[pitch:].copy_(rope)
+        self._blocks_pair(xs, L, pitch, tab.view(nb, R, 6, C), row_idx, ridx2, rope, rope2, kv_t, [n for _, n, _ in legs],
+                          [w for _, _, w in legs], kv_i, n_img)
+        ridx_new = row_idx[n_hist:] if row_idx is not None else None
+        return tuple(self._head(xs[o + n_hist:o + L], ridx_new, e, R, grid) for o in (0, pitch))
+
+    def _blocks_pair(self, xs, L, pitch, tab, row_idx, ridx2, rope, rope2, kv_t, n_txt, txt_w, kv_i, n_img):
+        """the blocks of forward_pair. xs fp32 [pitch + L, C]: rows [0, L) hold the embedded tokens on entry, both legs' outputs on exit
+        (leg 1 at row `pitch`). The same kernel calls as _blocks, on the stacked rows."""
+        m = self.model
+        C, H, Fd, eps = m.dim, m.num_heads, m.ffn_dim, m.eps
+        M = pitch + L
+        # rows and V^T columns exist up to a whole key tile behind leg 1 as well (zeros nobody writes): YUME_ATTN_KV_PADDED per leg
+        h = self._buf("h_p", (M, C), torch.bfloat16)
+        qk = self._buf("qk_p", (2 * pitch, 2 * C), torch.bfloat16, zero=True)
+        vt = self._buf("vt_p", (C, 2 * pitch), torch.bfloat16, zero=True)
+        att = self._buf("att_p", (M, C), torch.bfloat16, zero=True)
+        ff = self._buf("ff_p", (M, Fd), torch.bfloat16)
+        ts = 6 * C
+        T = self._timed
+        # (the register-staged kernel of the cross-check mode has no segmented form: the 4-wave LDS-DMA kernel then)
+        txt_variant = 2 if self.attn_variant == 1 else self.attn_variant
+        if pitch > L:
+            xs[L:pitch].zero_()                                         # the gap starts every call as a zero token ...
+            att[L:pitch].zero_()                                        # ... whose attention rows only the image branch adds to
+        for i, d in enumerate(self.P["blocks"]):
+            tb = tab[i]
+            shift_sa, scale_sa, gate_sa = tb[:, 0], tb[:, 1], tb[:, 2]
+            shift_ff, scale_ff, gate_ff = tb[:, 3], tb[:, 4], tb[:, 5]
+            # --- self attention: block 0 once, on the L rows both legs share; later blocks over the stacked rows, one attention launch per leg
+            n, ri, ro = (L, row_idx, rope) if i == 0 else (M, ridx2, rope2)
+            T("adaln", ops.adaln_modulate, xs[:n], scale_sa, shift_sa, ts, ri, True, h[:n], 0, eps)
+            T("gemm_qkv", ops.gemm_bf16, h[:n], d["wqkv"], d["bqkv"], qk[:n], EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+            T("rmsnorm_rope", ops.rmsnorm_rope, qk[:n], C, 2, d["nqk"], self.qk_eps, ro)
+            for o in ((0,) if i == 0 else (0, pitch)):
+                T("attn_self", ops.attn_fwd, qk[o:o + L, :C], qk[o:o + L, C:], vt[:, o:o + pitch], att[o:o + L], L, L, H, variant=self.attn_variant,
+                  q_prescaled=self.q_prescale, kv_padded=True)
+            T("gemm_o", ops.gemm_bf16, att[:n], d["wo"], d["bo"], xs[:n], EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ri, variant=self.gemm_variant)
+            if i == 0:
+                xs[pitch:].copy_(xs[:L])                                # the legs part here
+            # --- cross attention
+            if "n3w" in d:
+                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
+            else:
+                ops.cast_bf16(xs, M, h)
+            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:M, :C], EPI_BF16, variant=self.gemm_variant)
+            T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M, :C], C, 1, d["nq_c"], self.qk_eps)
+            T("attn_cross", ops.attn_fwd_seg, qk[:M, :C], [kc[:, i * C:(i + 1) * C] for kc, _ in kv_t], [v[i * C:(i + 1) * C] for _, v in kv_t],
+              att, L, pitch, n_txt, H, variant=txt_variant, q_prescaled=self.q_prescale, kv_padded=True, last_key_weights=txt_w)
+            if n_img:
+                T("attn_cross", ops.attn_fwd, qk[:M, :C], kv_i[0][:, i * C:(i + 1) * C], kv_i[1][i * C:(i + 1) * C], att, M, n_img, H, accumulate=True,
+                  variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
+            T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
+            # --- FFN
+            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx2, True, h, 0, eps)
+            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
+            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ridx2, variant=self.gemm_variant)
 
     def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_last_weight=1.0):
         """Blocks + head on this rank's token chunk (sequence_parallel.py:121-152: chunk after the embeddings, gather

@@ -249,6 +249,53 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     return out
 
 
+def attn_fwd_seg(q, ks, vts, out, Lq_seg, seg_pitch, Lks, H, scale=None, accumulate=False, variant=0, q_prescaled=False, kv_padded=False,
+                 last_key_weights=None):
+    """Segmented attention (yume_attn_fwd_seg): segment s = the rows [s * seg_pitch, s * seg_pitch + Lq_seg) of q and out, attending over
+    ks[s] / vts[s] with Lks[s] keys whose last one counts last_key_weights[s] times (None: every weight 1). One launch for all segments;
+    the rows of the pitch gap are neither read nor written. All ks (and all vts) share one row stride. kv_padded: as for attn_fwd, for
+    every segment. variants 0, 2 (4-wave LDS-DMA kernel) and 10 (short-key kernel, every Lks[s] <= 128)."""
+    lib = _lib.load()
+    nseg = len(ks)
+    if nseg < 1 or len(vts) != nseg or len(Lks) != nseg or (last_key_weights is not None and len(last_key_weights) != nseg):
+        raise RuntimeError("yume_amd.attn_fwd_seg: ks, vts, Lks and last_key_weights must list the same number (>= 1) of segments")
+    _dev(q, "q", torch.bfloat16)
+    _dev(out, "out", torch.bfloat16)
+    if nseg == 1:
+        ensure_counters(q.device)          # (one segment is attn_fwd's call, with attn_fwd's kernel choice)
+    qp, ldq = _rows(q, "q")
+    op, ldo = _rows(out, "out")
+    rows =(nseg - 1) * seg_pitch + Lq_seg
+    if q.shape[0] < rows or out.shape[0] < rows or q.shape[1] < H * 128 or out.shape[1] < H * 128:
+        raise RuntimeError(f"yume_amd.attn_fwd_seg: q {tuple(q.shape)} / out {tuple(out.shape)} do not hold {rows} rows of {H} heads")
+    kps, vps, ldk, ldv = [], [], None, None
+    for s, (k, vt, Lk) in enumerate(zip(ks, vts, Lks)):
+        _dev(k, f"ks[{s}]", torch.bfloat16)
+        _dev(vt, f"vts[{s}]", torch.bfloat16)
+        kp, lk = _rows(k, f"ks[{s}]")
+        vp, lv = _rows(vt, f"vts[{s}]")
+        if (ldk, ldv) not in ((None, None), (lk, lv)):
+            raise RuntimeError("yume_amd.attn_fwd_seg: every segment's k (and vt) must have the same row stride")
+        ldk, ldv = lk, lv
+        Lp = (Lk + 63) // 64 * 64 if kv_padded else Lk
+        need = k.storage_offset() + (Lp - 1) * lk + H * 128
+        if k.shape[0] < Lk or vt.shape[0] < H * 128 or vt.shape[1] < Lp or need > k.untyped_storage().nbytes() // k.element_size():
+            raise RuntimeError(f"yume_amd.attn_fwd_seg: segment {s}: k {tuple(k.shape)} / vt {tuple(vt.shape)} do not hold {Lp} keys of {H} heads")
+        kps.append(kp)
+        vps.append(vp)
+    if scale is None:
+        scale = 1.0 / math.sqrt(128.0)
+    import ctypes
+    karr, varr = (ctypes.c_void_p * nseg)(*kps), (ctypes.c_void_p * nseg)(*vps)
+    larr = (ctypes.c_int64 * nseg)(*[int(x) for x in Lks])
+    warr = None if last_key_weights is None else (ctypes.c_float * nseg)(*[float(w) for w in last_key_weights])
+    flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
+    rc = lib.yume_attn_fwd_seg(qp, ldq, karr, ldk, varr, ldv, op, ldo, nseg, Lq_seg, seg_pitch, larr, H, scale, 1 if accumulate else 0, flags,
+                               warr, _stream())
+    _lib.check(rc, "yume_attn_fwd_seg")
+    return out
+
+
 def linear_smallm_f32(x, w, bias, out, in_act=0, out_act=0, add_table=None):
     lib = _lib.load()
     _dev(x, "x", torch.float32)

@@ -32,13 +32,23 @@ def make_velocity_5b(model, context, seq_len, n_hist_tok, n_new_tok, sigmas, lfz
     return velocity
 
 
-def make_velocity_14b(model, arg_c, arg_null, sigmas, guide=5.0, rand_num_img=0.6, lfz=None):
-    """14B forward with classifier-free guidance: uncond + 5.0 * (cond - uncond) (sample.py:774-779)."""
+def make_velocity_14b(model, arg_c, arg_null, sigmas, guide=5.0, rand_num_img=0.6, lfz=None, fused=False):
+    """14B forward with classifier-free guidance: uncond + 5.0 * (cond - uncond) (sample.py:774-779).
+    fused: both legs in ONE model.forward_cfg call (arg_c and arg_null must then differ in `context` only, as they do in the reference);
+    the default stays two forward calls."""
     dev = next(model.parameters()).device
     kw = {} if lfz is None else {"latent_frame_zero": lfz}
+    if fused:
+        other = {k: v for k, v in arg_c.items() if k != "context"}
+        if sorted(other) != sorted(k for k in arg_null if k != "context") or any(arg_null[k] is not v for k, v in other.items()):
+            raise ValueError("make_velocity_14b(fused=True): arg_c and arg_null must share every argument but `context`")
 
     def velocity(latent, i):
         t = torch.tensor([sigmas[i] * 1000.0], device=dev)
+        if fused:
+            c, u = model.forward_cfg([latent], t=t, context=arg_c["context"], context_null=arg_null["context"], rand_num_img=rand_num_img,
+                                     **kw, **other)
+            return u + guide * (c - u)
         c = model([latent], t=t, rand_num_img=rand_num_img, **kw, **arg_c)[0]
         u = model([latent], t=t, rand_num_img=rand_num_img, **kw, **arg_null)[0]
         return u + guide * (c - u)

@@ -106,3 +106,22 @@ class WanModel(_Base):
                                       else clip_fea, packed=packed, lfz=latent_frame_zero,
                                       n_sel=(u.shape[1] - 9) if packed else None, cache=blk_cache)
         return out, (cache if cache_sample and return_cache else None)
+
+    def forward_cfg(self, x, t, context, context_null, seq_len, clip_fea=None, y=None, rand_num_img=None, enable_mask=False,
+                    latent_frame_zero=9, cache_sample=False, cache=None, return_cache=False, cache_list=None):
+        """The two forwards of a classifier-free-guidance step (fastvideo/sample/sample.py:774-779: same x, t, y and clip_fea, two prompts)
+        in one pass (DiTEngine.forward_pair). Arguments as for forward, with the unconditional prompt in context_null. Returns
+        (cond, uncond): fp32 [C_out, F', H, W] each, what forward(...)[0] returns for that context. The block-residual cache
+        (cache_sample) is not implemented for the pair."""
+        assert clip_fea is not None and y is not None
+        if len(x) != 1 or len(y) != 1 or len(context) != 1 or len(context_null) != 1:
+            raise NotImplementedError("yume_amd 14B WanModel.forward_cfg: one sample with its two prompts per call — got %d" % len(x))
+        if enable_mask:
+            raise NotImplementedError("enable_mask (MDT token masking) is a training-time path")
+        if cache_sample:
+            raise NotImplementedError("forward_cfg does not implement the block-residual cache (cache_sample); use two forward calls")
+        u = torch.cat([x[0], y[0]], dim=0)
+        packed = rand_num_img is not None and rand_num_img >= 0.4
+        return self.engine.forward_pair(u, t.reshape(-1)[:1], context[0], context_null[0],
+                                        clip_fea=clip_fea[0] if clip_fea.dim() == 3 else clip_fea, packed=packed, lfz=latent_frame_zero,
+                                        n_sel=(u.shape[1] - 9) if packed else None)

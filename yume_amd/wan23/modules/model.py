@@ -316,3 +316,18 @@ class WanModel(nn.Module):
                 ti = t[i:i + 1] if t.dim() >= 1 and t.shape[0] == len(x) else t
             outs.append(self.engine.forward_one(u, ti, context[i], packed=bool(flag), lfz=latent_frame_zero))
         return outs
+
+    def forward_cfg(self, x, t, context, context_null, seq_len, enable_mask=False, y=None, latent_frame_zero=8, input_ids=None, flag=True):
+        """The two forwards of a classifier-free-guidance step in one pass (DiTEngine.forward_pair): x, t, y and the keyword arguments as
+        for forward (one sample), context and context_null the conditional and the unconditional prompt. Returns (cond, uncond), each what
+        forward(...)[0] returns for that context."""
+        if enable_mask:
+            raise NotImplementedError("enable_mask (MDT token masking) is a training-time path, not part of the "
+                                      "inference hot path this implementation covers")
+        if len(x) != 1 or len(context) != 1 or len(context_null) != 1:
+            raise NotImplementedError("forward_cfg takes one sample with its two prompts (batches of unrelated samples are not implemented)")
+        if self.model_type == "i2v":
+            assert y is not None
+        u = x[0] if y is None else torch.cat([x[0], y[0]], dim=0)
+        ti = t if flag else (t[:1] if t.dim() >= 1 and t.shape[0] == 1 else t)
+        return self.engine.forward_pair(u, ti, context[0], context_null[0], packed=bool(flag), lfz=latent_frame_zero)
