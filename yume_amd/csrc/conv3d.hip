@@ -289,6 +289,8 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
         hp.tiles_h = (int)((Ho + conv_halo::TH - 1) / conv_halo::TH);
         const int64_t nt = To * hp.tiles_h * hp.tiles_w;
         YUME_REQUIRE(nt < (1ll << 31), "conv3d_cl: too many tiles");
+        static const bool log_on = [] { const char* v = getenv("YUME_CONV_LOG"); return v && atoi(v) != 0; }();
+        if (log_on) fprintf(stderr, "[conv3d_cl] halo M=%lld Cin=%lld Cout=%lld k=%dx%dx%d\n", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw);
         hipLaunchKernelGGL(conv_halo::conv_halo16_kernel<0>, dim3((unsigned)nt), dim3(256), 0, s, hp);
         YUME_CHECK_LAUNCH("conv3d_cl");
         return YUME_OK;
@@ -323,7 +325,7 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
                 q.cout = inst;
             }
             if (ups)
-                rc = addep ? -2 : conv_halo_n::launch_inst<6, 4, 8, 64, 8, true>(q, To, Ho, Wo, 0, s);
+                rc = conv_halo_n::launch_inst<6, 4, 8, 64, 8, true>(q, To, Ho, Wo, 0, s);     // (applies(): the plain epilogue only)
             else if (inst == 16)
                 rc = conv_halo_n::launch_inst<1, 8, 8, 64, 4>(q, To, Ho, Wo, addep, s);
             else if (inst == 96)
@@ -331,7 +333,7 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
             else
                 rc = conv_halo_n::launch_inst<10, 4, 4, 64, 4>(q, To, Ho, Wo, addep, s);
         }
-        YUME_REQUIRE(rc == 0, "conv3d_cl: too many tiles (or an upsample convolution with a shortcut)");
+        YUME_REQUIRE(rc == 0, "conv3d_cl: too many tiles");
         YUME_CHECK_LAUNCH("conv3d_cl");
         return YUME_OK;
     }
@@ -360,12 +362,13 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
             if (log_on) fprintf(stderr, "[conv3d_cl] w4   M=%lld Cin=%lld Cout=%lld k=%dx%dx%d ups=%d tiles=%d\n", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw, (int)ups, p2.tiles_m * p2.tiles_n);
             return gemm_w4::launch_conv_w4(e2, p, cv, e, s, "conv3d_cl");
         }
-        {
-            static const bool log_on = [] { const char* v = getenv("YUME_CONV_LOG"); return v && atoi(v) != 0; }();
-            if (log_on) fprintf(stderr, "[conv3d_cl] %s M=%lld Cin=%lld Cout=%lld k=%dx%dx%d stride=%d,%d,%d ups=%d\n", big ? "g256" : "g128", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw, st, sh, sw, (int)ups);
-        }
     }
-    if ((Cin % BK) == 0 && !ups && kh * kw <= 32) {
+    const bool fast = (Cin % BK) == 0 && !ups && kh * kw <= 32;
+    {
+        static const bool log_on = [] { const char* v = getenv("YUME_CONV_LOG"); return v && atoi(v) != 0; }();
+        if (log_on) fprintf(stderr, "[conv3d_cl] %s M=%lld Cin=%lld Cout=%lld k=%dx%dx%d stride=%d,%d,%d ups=%d loader=%s\n", big ? "g256" : "g128", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw, st, sh, sw, (int)ups, fast ? "fast" : "generic");
+    }
+    if (fast) {
         ConvAFast af = {};
         af.x = al.x; af.cache = al.cache; af.zero = al.zero; af.ldc = al.ldc;
         af.Tin = al.Tin; af.Hin = al.Hin; af.Win = al.Win; af.Cin = al.Cin;

@@ -335,7 +335,8 @@ inline bool applies(int64_t Cin, int64_t Cout, int kt, int kh, int kw, int st, i
     if (!on || st != 1 || sh != 1 || sw != 1 || kh != 3 || kw != 3 || ph != 1 || pw != 1) return false;
     if (!((kt == 3 && pt == 2) || (kt == 1 && pt == 0))) return false;
     if (epi != YUME_EPI_BF16 && epi != YUME_CONV_EPI_ADD && epi != YUME_CONV_EPI_RMS_SILU) return false;
-    if (epi == YUME_CONV_EPI_RMS_SILU && (ups || (Cout != 96 && Cout != 160))) return false;      // the whole channel row in one workgroup
+    if (ups && epi != YUME_EPI_BF16) return false;                                       // the folded upsample has the plain epilogue only
+    if (epi == YUME_CONV_EPI_RMS_SILU && Cout != 96 && Cout != 160) return false;      // the whole channel row in one workgroup
     if (instance(Cin, Cout, ups) == 0) return false;
     if (ups ? (Ho != 2 * Hin || Wo != 2 * Win || kt != 1) : (Ho != Hin || Wo != Win)) return false;
     if ((ldc % 8) != 0 || (ldw % 8) != 0 || (ldo % 4) != 0 || ldo < Cout || (Cout % 4) != 0 || (epi == YUME_CONV_EPI_ADD && ((ldadd % 4) != 0 || ldadd < Cout))) return false;
