@@ -247,7 +247,11 @@ int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
  *              otherwise the segmented 4-wave LDS-DMA kernel;
  * variant 10 = insists on the short-key kernel (YUME_EINVAL when some Lk[s] > 128 or the alignment fails); variant 2 on the 4-wave kernel;
  * any other variant: YUME_EUNSUP (the message names it).
- * nseg == 1 is yume_attn_fwd_kw(Q, .., K[0], .., Vt[0], .., Lq_seg, Lk[0], .., last_key_weight[0]): same kernel choice, same bits. */
+ * nseg == 1 is yume_attn_fwd_kw(Q, .., K[0], .., Vt[0], .., Lq_seg, Lk[0], .., last_key_weight[0]): same kernel choice, same bits.
+ * env YUME_ATTN_LOG=1 (read once per process, beside YUME_ATTN_V8, YUME_ATTN_SHORT and YUME_ATTN_RK): every call of the four entry points
+ *    prints one line on stderr that names the kernel it runs on (v1, v2, v2w = v2 with the weighted last key, v4, v7, v8, rk, short,
+ *    seg_short, seg_v2), for v7 / v8 the plan (tail_qb, splits; v8 also its workgroup count nwg), then the shape, the row strides and the
+ *    flags. Host code only: the kernels are the same with the switch on. tests/test_attn_routes_gpu.py reads it back. */
 int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* K, int64_t ldk, const void* const* Vt, int64_t ldvt,
                       void* O, int64_t ldo, int64_t nseg, int64_t Lq_seg, int64_t seg_pitch, const int64_t* Lk, int64_t H,
                       float scale, int accumulate, int variant, const float* last_key_weight, void* stream);

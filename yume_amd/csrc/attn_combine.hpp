@@ -5,6 +5,8 @@
 
 namespace {
 
+constexpr float FAR_BELOW = -100.0f;       // a piece this far under the row's base takes its factor 2^(m_s - m) in two halves
+
 // merge the key-range pieces of the v7 / v8 kernels: O = sum_s O_s 2^(m_s - m) / sum_s l_s 2^(m_s - m), m = max_s m_s (fixed order)
 __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml, int splits,
                                                            int64_t rows, int H, unsigned short* __restrict__ O, int64_t ldo, int q_lo,
@@ -20,9 +22,21 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
         float l = 0.f;
         for (int s = 0; s < splits; ++s) {
             const float* ml = part_ml + ((s * rows + r) * H + h) * 2;
-            const float a = __builtin_amdgcn_exp2f(ml[0] - m);
-            l += ml[1] * a;
-            acc += *reinterpret_cast<const f32x4*>(part_o + (s * rows + r) * ((int64_t)H * D) + h * D + 4 * c4) * a;
+            const f32x4 o = *reinterpret_cast<const f32x4*>(part_o + (s * rows + r) * ((int64_t)H * D) + h * D + 4 * c4);
+            const float d = ml[0] - m;
+            if (d < FAR_BELOW) {
+                // exp2(d) itself would fall into the denormal range, which v_exp_f32 flushes to 0, and with it a piece that is no small
+                // share of the row: an in-range base-free piece comes with the base 0 and a row sum of up to 2^120, beside a sibling that
+                // was redone on the robust body with a base above 126 (tests/attn_cases.py, pattern `peak`). The factor in two halves:
+                // each is normal down to d = -252, and below that the piece is under 2^-130 of the row.
+                const float h2 = __builtin_amdgcn_exp2f(0.5f * d);
+                l += (ml[1] * h2) * h2;
+                acc += (o * h2) * h2;
+            } else {
+                const float a = __builtin_amdgcn_exp2f(d);
+                l += ml[1] * a;
+                acc += o * a;
+            }
         }
         const float inv = 1.0f / l;
         float v0 = acc[0] * inv, v1 = acc[1] * inv, v2 = acc[2] * inv, v3 = acc[3] * inv;

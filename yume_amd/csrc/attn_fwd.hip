@@ -46,6 +46,12 @@ static bool attn_short_auto() {
     static const bool on = [] { const char* v = getenv("YUME_ATTN_SHORT"); return v ? atoi(v) != 0 : YUME_ATTN_SHORT_DEFAULT; }();
     return on;
 }
+// YUME_ATTN_LOG=1: one line per call on stderr with the kernel that takes it (and, for the planned kernels, the plan): what
+// tests/test_attn_routes_gpu.py reads back
+static bool attn_log_on() {
+    static const bool on = [] { const char* v = getenv("YUME_ATTN_LOG"); return v && atoi(v) != 0; }();
+    return on;
+}
 static int cu_count() {
     static thread_local int n[64] = {};
     int dev = 0;
@@ -148,6 +154,30 @@ static int choose(const AttnArgs& c, int variant, bool kv_pad, const void* works
 // ---- launch --------------------------------------------------------------------------------------------------------------------------------
 // the v7 / v8 kernels over all query rows: whole blocks below pl.tail_qb, the rest cut into pl.splits key ranges whose partial results go
 // to `workspace` (checked by usable_plan) and through the merge pass
+// workgroups of the persistent kernel: one per item (whole block or piece), at most one per CU. b: nqb / tail_qb / splits set
+static int v8_workgroups(const AttnArgs& b) {
+    int64_t items = 0;
+    for (int y = 0; y < 8; ++y) items += (int64_t)((b.H + 7 - y) >> 3) * (b.tail_qb + (int64_t)(b.nqb - b.tail_qb) * b.splits);
+    return (int)(items < cu_count() ? items : cu_count());
+}
+
+// the YUME_ATTN_LOG line of one yume_attn_fwd / _ws / _kw call
+static void log_choice(const Choice& ch, const AttnArgs& a, bool kv_pad, const void* workspace) {
+    static const char* const names[] = {"v1", "v2", "v2w", "v4", "v7", "v8", "rk", "short"};
+    char plan[96] = "";
+    if (ch.kernel == Kernel::V7 || ch.kernel == Kernel::V8) {
+        int n = snprintf(plan, sizeof plan, " tail_qb=%lld splits=%d", (long long)ch.plan.tail_qb, ch.plan.splits);
+        if (ch.kernel == Kernel::V8) {
+            AttnArgs b = whole_blocks(a, QB4);
+            if (ch.plan.splits > 1) { b.tail_qb = (int)ch.plan.tail_qb; b.splits = ch.plan.splits; }
+            snprintf(plan + n, sizeof plan - n, " nwg=%d", v8_workgroups(b));
+        }
+    }
+    fprintf(stderr, "[attn_fwd] %s%s Lq=%d Lk=%d H=%d ldq=%lld ldk=%lld ldvt=%lld ldo=%lld prescaled=%d kv_padded=%d accumulate=%d last_w=%g ws=%d\n",
+            names[(int)ch.kernel], plan, a.Lq, a.Lk, a.H, (long long)a.ldq, (long long)a.ldk, (long long)a.ldvt, (long long)a.ldo, a.q_prescaled,
+            kv_pad ? 1 : 0, a.accumulate, (double)a.last_w, workspace ? 1 : 0);
+}
+
 static void launch_planned(const Choice& ch, const AttnArgs& a, void* workspace, hipStream_t st) {
     AttnArgs b = whole_blocks(a, QB4);
     const attn_plan::Plan& pl = ch.plan;
@@ -158,10 +188,7 @@ static void launch_planned(const Choice& ch, const AttnArgs& a, void* workspace,
         b.part_ml = b.part_o + (int64_t)pl.splits * attn_plan::split_rows(pl, a.Lq) * a.H * D;
     }
     if (ch.kernel == Kernel::V8) {
-        int64_t items = 0;
-        for (int y = 0; y < 8; ++y) items += (int64_t)((a.H + 7 - y) >> 3) * (b.tail_qb + (int64_t)(b.nqb - b.tail_qb) * b.splits);
-        const int nwg = (int)(items < cu_count() ? items : cu_count());
-        yume_attn8_launch(b, ch.counters, nwg, st);
+        yume_attn8_launch(b, ch.counters, v8_workgroups(b), st);
     } else {
         yume_attn7_launch(b, st);
     }
@@ -198,6 +225,7 @@ static int attn_fwd_impl(const void* Q, int64_t ldq, const void* K, int64_t ldk,
     Choice ch;
     const int rc = choose(a, variant, kv_pad != 0, workspace, workspace_bytes, ch);
     if (rc != YUME_OK) return rc;
+    if (attn_log_on()) log_choice(ch, a, kv_pad != 0, workspace);
 
     switch (ch.kernel) {
         case Kernel::SHORT: attn_short::launch(a, cu_count(), st); break;
@@ -279,7 +307,14 @@ extern "C" int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* 
     hipStream_t st = (hipStream_t)stream;
     const bool fits = attn_seg::short_fits(a);
     if (v == 10) YUME_REQUIRE(fits, "attn_fwd_seg: variant 10 (short-key kernel) needs ldo %% 8 == 0 and a 16-byte aligned O");
-    if (v == 10 || (v == 0 && fits && attn_short_auto())) attn_seg::launch_short(a, cu_count(), st);
+    const bool seg_short = v == 10 || (v == 0 && fits && attn_short_auto());
+    if (attn_log_on()) {
+        fprintf(stderr, "[attn_fwd_seg] %s nseg=%d Lq_seg=%d seg_pitch=%d H=%d Lk=", seg_short ? "seg_short" : "seg_v2", a.nseg, a.Lq_seg, a.seg_pitch, a.H);
+        for (int s = 0; s < a.nseg; ++s) fprintf(stderr, "%s%d", s ? "," : "", a.Lk[s]);
+        fprintf(stderr, " ldq=%lld ldk=%lld ldvt=%lld ldo=%lld prescaled=%d kv_padded=%d accumulate=%d\n", (long long)ldq, (long long)ldk,
+                (long long)ldvt, (long long)ldo, (flags & YUME_ATTN_Q_PRESCALED) ? 1 : 0, (flags & YUME_ATTN_KV_PADDED) ? 1 : 0, accumulate);
+    }
+    if (seg_short) attn_seg::launch_short(a, cu_count(), st);
     else attn_seg::launch_v2(a, st);
     YUME_CHECK_LAUNCH("attn_fwd_seg");
     return YUME_OK;
