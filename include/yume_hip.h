@@ -255,6 +255,29 @@ int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
 int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* K, int64_t ldk, const void* const* Vt, int64_t ldvt,
                       void* O, int64_t ldo, int64_t nseg, int64_t Lq_seg, int64_t seg_pitch, const int64_t* Lk, int64_t H,
                       float scale, int accumulate, int variant, const float* last_key_weight, void* stream);
+/* BATCHED self-attention (r12): ONE launch serves nseg (1 .. 8) attention problems of ONE shape that are stacked in the same buffers. Segment s
+ * owns the rows [s * q_pitch, s * q_pitch + Lq_seg) of Q and O, the rows [s * k_pitch, s * k_pitch + Lk_seg) of K and the columns of Vt from
+ * s * k_pitch on. Rows and columns in the pitch gaps are neither read for a result nor written.
+ * replaces: B separate calls of the model for B samples (the reference's packed path is single-sample by construction,
+ *           wan/modules/model.py:474-475,1011), run as one pass over the stacked rows of all of them (DiTEngine.forward_batch).
+ * ldq, ldk, ldvt, ldo, H, scale, accumulate, YUME_ATTN_Q_PRESCALED / YUME_ATTN_KV_PADDED (per segment): as for yume_attn_fwd_ws.
+ * Checks (YUME_EINVAL by name): nseg in [1, 8]; q_pitch >= Lq_seg; k_pitch a multiple of 64 and >= ceil(Lk_seg/64)*64;
+ *    ldvt >= (nseg-1)*k_pitch + ceil(Lk_seg/64)*64; Q, K, Vt, O non-NULL and 16-byte aligned; a workspace that is given is 16-byte aligned and
+ *    holds yume_attn_batch_workspace_bytes(nseg, Lq_seg, Lk_seg, H) bytes (NULL: no query block is cut into key ranges).
+ * variant 0  = the persistent kernel over (segment, head) pairs (attn_batch8.hip: attn_fwd8.hip's kernel, an item's head being the virtual
+ *              head s * H + h; the plan is that of nseg * H heads) when both flags are set, a counter workspace is registered, Lk_seg >= 1536,
+ *              Lq_seg >= 256 and Lq_seg * ldq * 2 + 512 < 2^32 — a limit on ONE segment's extent: a segment's base is a 64-bit offset, the stacked
+ *              buffers may exceed 4 GiB; otherwise one launch of the segmented 4-wave LDS-DMA kernel (yume_attn_fwd_seg's) over views;
+ * variant 8  = insists on the persistent kernel: the conditions are REQUIRED, with Lk_seg >= 512; variant 2 insists on the 4-wave kernel;
+ * any other variant: YUME_EUNSUP (the message names it).
+ * Same arithmetic per key tile in the same order as yume_attn_fwd's variant 8: segment s is bit-identical to that call on the segment's
+ *    views whenever both carry the same plan. nseg == 1 is yume_attn_fwd_ws: same kernel choice, same bits.
+ * env YUME_ATTN_LOG=1: one line per call, `[attn_fwd_batch] batch_v8 tail_qb=.. splits=.. nwg=.. nseg=.. ...` or `[attn_fwd_batch] seg_v2 ...`. */
+int64_t yume_attn_batch_workspace_bytes(int64_t nseg, int64_t Lq_seg, int64_t Lk_seg, int64_t H);
+int yume_attn_fwd_batch(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                        void* O, int64_t ldo, int64_t nseg, int64_t Lq_seg, int64_t q_pitch,
+                        int64_t Lk_seg, int64_t k_pitch, int64_t H, float scale, int accumulate, int variant,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- small-M fp32 linear (time embedding MLP) ---------------------------------------------
  * replaces: wan23/modules/model.py:459-461,803-812 (time_embedding, time_projection under

@@ -1,4 +1,5 @@
-// attn_args.hpp — launch arguments shared by the attention kernels (attn_fwd.hip and its kernel headers, attn_fwd7.hip, attn_fwd8.hip).
+// attn_args.hpp — launch arguments shared by the attention kernels (attn_fwd.hip and its kernel headers, attn_fwd7.hip, attn_fwd8.hip,
+// attn_batch8.hip).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -33,3 +34,14 @@ void yume_attn7_launch(const AttnArgs& a, hipStream_t st);
 // a.tail_qb / a.splits, as for attn_fwd7) are drawn by ticket from `counters`, one 64-byte set of the caller's counter workspace
 // (counters.hpp). Requires a.q_prescaled, K readable and V^T finite up to a whole number of 64-key tiles, every item >= 5 key tiles.
 void yume_attn8_launch(const AttnArgs& a, int* counters, int nwg, hipStream_t st);
+
+// A batch launch (yume_attn_fwd_batch): nseg problems of one shape stacked in the same buffers. The AttnArgs beside it describe segment 0 with
+// H = nseg * (heads per segment) VIRTUAL heads; segment s lies these many elements further on.
+struct AttnBatchSeg {
+    int H;                                  // heads per segment: virtual head hv = s * H + h
+    int64_t q_step, k_step, o_step;         // q_pitch * ldq, k_pitch * ldk, q_pitch * ldo
+    int64_t vt_step;                        // k_pitch (columns of V^T)
+    int64_t part_o_step, part_ml_step;      // floats between two segments' slices of part_o / part_ml
+};
+// attn_batch8.hip: attn_fwd8.hip's kernel over the (segment, head) pairs of a batch launch; a, counters, nwg as for yume_attn8_launch
+void yume_attn_batch8_launch(const AttnArgs& a, const AttnBatchSeg& sg, int* counters, int nwg, hipStream_t st);

@@ -1,5 +1,6 @@
 // attn_fwd.hip — exact-softmax attention forward for head_dim 128, bf16 in / fp32 accumulate / bf16 out (gfx950): the C-ABI entry points
-// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_fwd_seg, yume_attn_workspace_bytes) and the dispatcher behind them:
+// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_fwd_seg, yume_attn_fwd_batch, yume_attn_workspace_bytes,
+// yume_attn_batch_workspace_bytes) and the dispatcher behind them:
 // validate -> choose -> launch.
 //
 // Seven kernels compute the same function (choose() picks; the tests compare them). Each lives in a file of its own with its design comment:
@@ -13,6 +14,7 @@
 //   attn_cross_rk_kernel  attn_cross_rk.hpp   448 < Lk <= 512: K and V^T resident in a workgroup's registers
 //   attn_short_kernel     attn_short.hpp      Lk <= 128: a head's K and V^T resident in one wave's registers (takes the weighted last key)
 // yume_attn_fwd_seg (several independent segments in one launch) has the segmented forms of the last two of its own: attn_seg.hpp.
+// yume_attn_fwd_batch (several stacked self-attention problems of one shape) has attn_fwd_kernel_v8's: attn_batch8.hip.
 // and attn_combine_kernel (attn_combine.hpp) merges the key-range pieces of a split v7 / v8 launch, planned by attn_plan.hpp.
 // The transposed formulation and the tile layouts the kernels share: attn_tile.hpp.
 #include "common.hpp"
@@ -317,5 +319,132 @@ extern "C" int yume_attn_fwd_seg(const void* Q, int64_t ldq, const void* const* 
     if (seg_short) attn_seg::launch_short(a, cu_count(), st);
     else attn_seg::launch_v2(a, st);
     YUME_CHECK_LAUNCH("attn_fwd_seg");
+    return YUME_OK;
+}
+
+// Batched self-attention (attn_batch8.hip): nseg problems of one shape stacked in the same Q / K / V^T / O buffers, q_pitch rows (Q, O) and
+// k_pitch rows (K) / columns (V^T) apart. nseg == 1 IS yume_attn_fwd_ws.
+static int64_t ceil_tile(int64_t Lk) { return (Lk + KT - 1) / KT * KT; }
+
+extern "C" int64_t yume_attn_batch_workspace_bytes(int64_t nseg, int64_t Lq_seg, int64_t Lk_seg, int64_t H) {
+    if (nseg <= 0 || Lq_seg <= 0 || Lk_seg <= 0 || H <= 0) return 0;
+    if (nseg == 1) return yume_attn_workspace_bytes(Lq_seg, Lk_seg, H);
+    if (!attn_plan::applies(attn_plan::V8, Lq_seg, Lk_seg)) return 0;
+    // one plan for the nseg * H virtual heads; every segment has its own slice of partial results
+    return nseg * attn_plan::workspace_bytes(attn_plan::plan(attn_plan::V8, Lq_seg, Lk_seg, nseg * H), Lq_seg, H);
+}
+
+extern "C" int yume_attn_fwd_batch(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                                   int64_t nseg, int64_t Lq_seg, int64_t q_pitch, int64_t Lk_seg, int64_t k_pitch, int64_t H, float scale,
+                                   int accumulate, int variant, void* workspace, int64_t workspace_bytes, void* stream) {
+    YUME_REQUIRE(nseg >= 1 && nseg <= ATTN_SEG_MAX, "attn_fwd_batch: nseg=%lld must be in [1, %d]", (long long)nseg, ATTN_SEG_MAX);
+    YUME_REQUIRE(Q && K && Vt && O, "attn_fwd_batch: NULL pointer");
+    YUME_REQUIRE(Lq_seg > 0 && Lk_seg > 0 && H > 0, "attn_fwd_batch: empty problem Lq_seg=%lld Lk_seg=%lld H=%lld", (long long)Lq_seg,
+                 (long long)Lk_seg, (long long)H);
+    YUME_REQUIRE(Lq_seg < (1ll << 30) && Lk_seg < (1ll << 30) && H < 65536 / ATTN_SEG_MAX, "attn_fwd_batch: dimension too large");
+    YUME_REQUIRE(q_pitch >= Lq_seg && q_pitch * nseg < (1ll << 30), "attn_fwd_batch: q_pitch=%lld must be >= Lq_seg=%lld (and nseg * q_pitch < 2^30)",
+                 (long long)q_pitch, (long long)Lq_seg);
+    YUME_REQUIRE((k_pitch % KT) == 0 && k_pitch >= ceil_tile(Lk_seg) && k_pitch * nseg < (1ll << 30),
+                 "attn_fwd_batch: k_pitch=%lld must be a multiple of 64 and >= %lld (Lk_seg=%lld in whole key tiles)", (long long)k_pitch,
+                 (long long)ceil_tile(Lk_seg), (long long)Lk_seg);
+    YUME_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldvt % 8) == 0 && (ldo % 4) == 0, "attn_fwd_batch: ldq/ldk/ldvt must be multiples of 8, ldo of 4");
+    YUME_REQUIRE(ldk < (1ll << 24) && ldvt < (1ll << 24), "attn_fwd_batch: ldk / ldvt too large for 32-bit tile offsets");
+    YUME_REQUIRE(ldvt >= (nseg - 1) * k_pitch + ceil_tile(Lk_seg), "attn_fwd_batch: ldvt=%lld must be >= (nseg-1)*k_pitch + Lk_seg in whole key tiles = %lld",
+                 (long long)ldvt, (long long)((nseg - 1) * k_pitch + ceil_tile(Lk_seg)));
+    YUME_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)Vt % 16) == 0 && ((uintptr_t)O % 16) == 0,
+                 "attn_fwd_batch: pointer alignment (Q, K, Vt, O: 16 bytes)");
+    const int flags = variant & (YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 2 && v != 8) {
+        yume_set_error("attn_fwd_batch: variant %d has no batch kernel (variants 0, 2 and 8 do)", v);
+        return YUME_EUNSUP;
+    }
+    const int64_t ws_need = yume_attn_batch_workspace_bytes(nseg, Lq_seg, Lk_seg, H);
+    if (workspace) {
+        YUME_REQUIRE(((uintptr_t)workspace % 16) == 0, "attn_fwd_batch: workspace must be 16-byte aligned");
+        YUME_REQUIRE(workspace_bytes >= ws_need, "attn_fwd_batch: workspace_bytes=%lld is below yume_attn_batch_workspace_bytes = %lld",
+                     (long long)workspace_bytes, (long long)ws_need);
+    }
+    if (nseg == 1)      // one segment is the plain call: same kernel choice, same bits
+        return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq_seg, Lk_seg, H, scale, accumulate, variant, workspace, workspace_bytes, stream);
+
+    const bool q_pre = (flags & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (flags & YUME_ATTN_KV_PADDED) != 0;
+    hipStream_t st = (hipStream_t)stream;
+    // the persistent kernel's own conditions, for ONE segment's extent (the segments' bases are 64-bit)
+    const bool p8_fits = q_pre && kv_pad && attn_plan::applies(attn_plan::V8, Lq_seg, Lk_seg) && Lq_seg * ldq * 2 + 512 < (1ll << 32);
+    if (v == 8)
+        YUME_REQUIRE(p8_fits, "attn_fwd_batch: variant 8 needs YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED, Lk_seg >= 512, Lq_seg >= 256 and "
+                              "Lq_seg * ldq < 2^31");
+    int* counters = nullptr;
+    if (v == 8 || (v == 0 && p8_fits && attn_plan::applies(attn_plan::V7, Lq_seg, Lk_seg) && attn8_enabled())) {
+        counters = yume_counters::next_set();
+        if (v == 8) YUME_REQUIRE(counters != nullptr, "attn_fwd_batch: variant 8 needs a registered counter workspace (yume_counter_workspace_init)");
+    }
+    if (counters) {
+        AttnArgs a{};
+        a.Q = (const unsigned short*)Q; a.ldq = ldq;
+        a.K = (const unsigned short*)K; a.ldk = ldk;
+        a.Vt = (const unsigned short*)Vt; a.ldvt = ldvt;
+        a.O = (unsigned short*)O; a.ldo = ldo;
+        a.Lq = (int)Lq_seg; a.Lk = (int)Lk_seg; a.H = (int)(nseg * H);        // virtual heads: what the queues and the plan see
+        a.q_prescaled = 1;
+        a.scale_log2 = 1.0f;
+        a.accumulate = accumulate;
+        a.splits = 1;
+        a.last_w = 1.0f;
+        AttnArgs b = whole_blocks(a, QB4);
+        attn_plan::Plan pl = attn_plan::plan(attn_plan::V8, Lq_seg, Lk_seg, nseg * H);
+        if (pl.splits > 1 && !workspace) pl = attn_plan::Plan{(Lq_seg + QB4 - 1) / QB4, 1};      // no scratch: whole query blocks
+        AttnBatchSeg sg{};
+        sg.H = (int)H;
+        sg.q_step = q_pitch * ldq; sg.k_step = k_pitch * ldk; sg.o_step = q_pitch * ldo; sg.vt_step = k_pitch;
+        if (pl.splits > 1) {
+            const int64_t rows = attn_plan::split_rows(pl, Lq_seg);
+            b.tail_qb = (int)pl.tail_qb;
+            b.splits = pl.splits;
+            sg.part_o_step = (int64_t)pl.splits * rows * H * D;
+            sg.part_ml_step = (int64_t)pl.splits * rows * H * 2;
+            b.part_o = reinterpret_cast<float*>(workspace);
+            b.part_ml = b.part_o + nseg * sg.part_o_step;
+        }
+        const int nwg = v8_workgroups(b);
+        if (attn_log_on())
+            fprintf(stderr, "[attn_fwd_batch] batch_v8 tail_qb=%lld splits=%d nwg=%d nseg=%d Lq_seg=%d q_pitch=%lld Lk_seg=%d k_pitch=%lld H=%d ldq=%lld "
+                            "ldk=%lld ldvt=%lld ldo=%lld accumulate=%d ws=%d\n", (long long)pl.tail_qb, pl.splits, nwg, (int)nseg, a.Lq, (long long)q_pitch,
+                    a.Lk, (long long)k_pitch, (int)H, (long long)ldq, (long long)ldk, (long long)ldvt, (long long)ldo, accumulate, workspace ? 1 : 0);
+        yume_attn_batch8_launch(b, sg, counters, nwg, st);
+        if (b.splits > 1) {
+            // the merge pass as it stands, once per segment: that segment's slice of the partial results, its O rows, H heads
+            for (int s = 0; s < (int)nseg; ++s) {
+                AttnArgs c = b;
+                c.H = (int)H;
+                c.O = b.O + s * sg.o_step;
+                c.part_o = b.part_o + s * sg.part_o_step;
+                c.part_ml = b.part_ml + s * sg.part_ml_step;
+                attn_combine::launch(c, QB4, st);
+            }
+        }
+        YUME_CHECK_LAUNCH("attn_fwd_batch");
+        return YUME_OK;
+    }
+    // the 4-wave segmented kernel (attn_seg.hpp) with K[s] / Vt[s] pointing into the stacked buffers and weights of 1
+    AttnSegArgs g{};
+    g.Q = (const unsigned short*)Q; g.ldq = ldq; g.ldk = ldk; g.ldvt = ldvt;
+    g.O = (unsigned short*)O; g.ldo = ldo;
+    for (int s = 0; s < (int)nseg; ++s) {
+        g.K[s] = (const unsigned short*)K + s * k_pitch * ldk;
+        g.Vt[s] = (const unsigned short*)Vt + s * k_pitch;
+        g.Lk[s] = (int)Lk_seg;
+        g.last_w[s] = 1.0f;
+    }
+    g.nseg = (int)nseg; g.Lq_seg = (int)Lq_seg; g.seg_pitch = (int)q_pitch; g.H = (int)H;
+    g.scale_log2 = q_pre ? 1.0f : scale * 1.4426950408889634f;
+    g.accumulate = accumulate;
+    if (attn_log_on())
+        fprintf(stderr, "[attn_fwd_batch] seg_v2 nseg=%d Lq_seg=%d q_pitch=%lld Lk_seg=%d k_pitch=%lld H=%d ldq=%lld ldk=%lld ldvt=%lld ldo=%lld "
+                        "prescaled=%d kv_padded=%d accumulate=%d\n", (int)nseg, (int)Lq_seg, (long long)q_pitch, (int)Lk_seg, (long long)k_pitch, (int)H,
+                (long long)ldq, (long long)ldk, (long long)ldvt, (long long)ldo, q_pre ? 1 : 0, kv_pad ? 1 : 0, accumulate);
+    attn_seg::launch_v2(g, st);
+    YUME_CHECK_LAUNCH("attn_fwd_batch");
     return YUME_OK;
 }

@@ -72,6 +72,16 @@ class DiTEngine:
         self._ctx_refs = None
         self._pair_ctx_key = None          # forward_pair's own conditioning cache (its K / V^T live in buffers of their own)
         self._pair_ctx_refs = None
+        self._batch_ctx_key = None         # ... and forward_batch's
+        self._batch_ctx_refs = None
+        # forward_batch: the variant handed to ops.attn_fwd_batch for the self-attention of the stacked samples (0 = automatic: the persistent
+        # kernel over (sample, head) pairs from 1536 keys on, the segmented 4-wave kernel below; 8 insists on the persistent kernel — tests
+        # run it at a small L that way)
+        self.batch_attn_variant = 0
+        # forward_pair: issue the self-attention of the blocks >= 1 as ONE ops.attn_fwd_batch launch over the two legs instead of one
+        # ops.attn_fwd launch per leg. Off by default = forward_pair as it was; env YUME_PAIR_SELF_BATCHED=1 turns it on (tools/batch_ab.py
+        # measures both).
+        self.pair_self_batched = os.environ.get("YUME_PAIR_SELF_BATCHED", "0") == "1"
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -469,10 +479,11 @@ class DiTEngine:
         return y
 
     # ------------------------------------------------------------------ one sample forward
-    def _prologue(self, u, t, packed, lfz, n_sel, pair=False):
+    def _prologue(self, u, t, packed, lfz, n_sel, pair=False, xs_rows=None):
         """what a forward does before the conditioning enters: the per-clip tables, the timestep rows, the patch embedding into the residual
         stream and the modulation table. Returns (xs, L, n_hist, grid, rope, R, row_idx, e, tab). pair: the residual stream is forward_pair's
-        stacked buffer (the embedding fills its first L rows)."""
+        stacked buffer (the embedding fills its first L rows). xs_rows: a function L -> the rows of the residual stream the embedding fills
+        (forward_batch: one sample's rows of its stacked buffer)."""
         m = self.model
         C, D = m.dim, m.dim // m.num_heads
         if D != 128:
@@ -532,7 +543,10 @@ class DiTEngine:
             row_idx = inv.to(torch.int32).contiguous()
 
         # --- embeddings
-        xs = self._buf("xs_p", (_round_up(L, 64) + L, C), torch.float32) if pair else self._buf("xs", (L, C), torch.float32)
+        if xs_rows is not None:
+            xs = xs_rows(L)
+        else:
+            xs = self._buf("xs_p", (_round_up(L, 64) + L, C), torch.float32) if pair else self._buf("xs", (L, C), torch.float32)
         off = 0
         for g in groups:
             self._embed_group(u, g, xs[off:off + g.ntok])
@@ -688,7 +702,10 @@ class DiTEngine:
             T("adaln", ops.adaln_modulate, xs[:n], scale_sa, shift_sa, ts, ri, True, h[:n], 0, eps)
             T("gemm_qkv", ops.gemm_bf16, h[:n], d["wqkv"], d["bqkv"], qk[:n], EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:n], C, 2, d["nqk"], self.qk_eps, ro)
-            for o in ((0,) if i == 0 else (0, pitch)):
+            if i > 0 and self.pair_self_batched:
+                T("attn_self", ops.attn_fwd_batch, qk[:M, :C], qk[:, C:], vt, att, 2, L, pitch, L, pitch, H, variant=self.batch_attn_variant,
+                  q_prescaled=self.q_prescale, kv_padded=True)
+            for o in (() if i > 0 and self.pair_self_batched else (0,) if i == 0 else (0, pitch)):
                 T("attn_self", ops.attn_fwd, qk[o:o + L, :C], qk[o:o + L, C:], vt[:, o:o + pitch], att[o:o + L], L, L, H, variant=self.attn_variant,
                   q_prescaled=self.q_prescale, kv_padded=True)
             T("gemm_o", ops.gemm_bf16, att[:n], d["wo"], d["bo"], xs[:n], EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ri, variant=self.gemm_variant)
@@ -711,6 +728,176 @@ class DiTEngine:
             T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx2, True, h, 0, eps)
             T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
             T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ridx2, variant=self.gemm_variant)
+
+    # ------------------------------------------------------------------ several samples in one pass
+    @torch.no_grad()
+    def forward_batch(self, us, ts, contexts, clip_feas=None, packed=True, lfz=8, n_sel=None, cache=None):
+        """B (2 .. 8) samples of ONE shape in one pass over their stacked rows: us, ts, contexts lists of what forward_one takes (the
+        timesteps, the prompts and their lengths are per sample), clip_feas a list or ONE tensor shared by all samples (14B); packed, lfz,
+        n_sel common. Returns a list of fp32 outputs, each what forward_one returns for that sample. B == 1 calls forward_one.
+
+        Sample s is at row s * pitch, pitch = ceil(L / 64) * 64 (the QKV GEMM writes V^T columns by stacked row and the attention kernels
+        fetch K rows / V^T columns in whole 64-key tiles, as in forward_pair); the rows between two samples are zero tokens that are never
+        keys and never returned. The prologue (patch embedding, time rows, modulation table) runs per sample into the stacked residual
+        stream and a stacked modulation table whose rows the row selector picks per sample (an explicit selector also where forward_one
+        passes none: t differs per sample). Every adaLN, cast, GEMM and RMSNorm+RoPE launch runs once over the stacked rows;
+        self-attention is ONE ops.attn_fwd_batch launch per block; the text cross-attention one ops.attn_fwd_seg launch, each sample over
+        its own K / V^T (with dedup_pad_keys its own n + 1 keys and last-key weight); the 14B image cross-attention one accumulating
+        ops.attn_fwd over all stacked rows when every sample carries the same clip_fea tensor, one accumulating ops.attn_fwd_seg with
+        per-sample image keys otherwise. Head and unpatchify run per sample.
+
+        cache_context keys on all prompts and clip_feas (own buffers: forward_one's and forward_pair's caches are not disturbed);
+        trim_last_block is ignored. Sequence parallelism and the block-residual cache are not implemented for the batch."""
+        B = len(us)
+        if len(ts) != B or len(contexts) != B:
+            raise RuntimeError(f"forward_batch: {B} samples, {len(ts)} timesteps, {len(contexts)} contexts")
+        if isinstance(clip_feas, torch.Tensor):
+            clip_feas = [clip_feas] * B
+        if clip_feas is not None and len(clip_feas) != B:
+            raise RuntimeError(f"forward_batch: {B} samples, {len(clip_feas)} clip_feas")
+        if cache is not None:
+            raise NotImplementedError("forward_batch does not implement the block-residual cache (cache_sample); use forward_one per sample")
+        if self.sp is not None:
+            raise NotImplementedError("forward_batch is not implemented under sequence parallelism (enable_sequence_parallel)")
+        if B == 1:
+            return [self.forward_one(us[0], ts[0], contexts[0], clip_fea=None if clip_feas is None else clip_feas[0], packed=packed, lfz=lfz,
+                                     n_sel=n_sel)]
+        if not 2 <= B <= 8:
+            raise RuntimeError(f"forward_batch takes 1 .. 8 samples per pass, got {B}")
+        if any(tuple(u.shape) != tuple(us[0].shape) for u in us):
+            raise RuntimeError("forward_batch: the samples of one pass must have one shape: " + ", ".join(str(tuple(u.shape)) for u in us))
+        self.ensure_packed()
+        m = self.model
+        C, nb = m.dim, len(self.P["blocks"])
+        n_img = 0
+        if self.family == "wan":
+            if clip_feas is None or any(c is None for c in clip_feas):
+                raise RuntimeError("clip_fea is required by the i2v model")
+            n_img = clip_feas[0].reshape(-1, clip_feas[0].shape[-1]).shape[0]
+            if any(c.reshape(-1, c.shape[-1]).shape[0] != n_img for c in clip_feas):
+                raise RuntimeError("forward_batch: every clip_fea must have the same number of image tokens")
+
+        # --- the prologue per sample, into the stacked residual stream, modulation table and time rows
+        state = {}
+
+        def rows_of(s):
+            def get(L):
+                pitch = _round_up(L, 64)
+                xs = self._buf("xs_b", ((B - 1) * pitch + L, C), torch.float32)
+                state["xs"] = xs
+                return xs[s * pitch:s * pitch + L]
+            return get
+        per, r_off = [], 0
+        for s in range(B):
+            _, L, n_hist, grid, rope, R, row_idx, e, tab = self._prologue(us[s], ts[s], packed, lfz, n_sel, xs_rows=rows_of(s))
+            # (e and tab are the engine's per-call buffers: the next sample's prologue overwrites them)
+            per.append((R, r_off, row_idx, e.clone(), tab.view(nb, R, 6 * C).clone()))
+            r_off += R
+        xs, RT = state["xs"], r_off
+        pitch = _round_up(L, 64)
+        M = (B - 1) * pitch + L
+        tabs = self._buf("tab_b", (nb, RT, 6 * C), torch.float32)
+        ridx = self._buf("ridx_b", (M,), torch.int32, zero=True)            # (the gaps: row 0 of the table)
+        ropes = self._buf("rope_b", (M,) + tuple(rope.shape[1:]), torch.float32, zero=True)    # (the gaps: a zero rotation)
+        for s, (R, off, row_idx, _, tab) in enumerate(per):
+            tabs[:, off:off + R].copy_(tab)
+            if row_idx is None:
+                ridx[s * pitch:s * pitch + L].fill_(off)
+            else:
+                torch.add(row_idx, off, out=ridx[s * pitch:s * pitch + L])
+            ropes[s * pitch:s * pitch + L].copy_(rope)
+            if s and pitch > L:
+                xs[s * pitch - (pitch - L):s * pitch].zero_()               # the gap in front of sample s starts every call as a zero token
+
+        # --- conditioning: every sample its own text K / V^T; the image K / V^T once when all samples share one clip_fea tensor
+        legs = []
+        for c in contexts:
+            n_txt, txt_w = m.text_len, 1.0
+            if self.dedup_pad_keys and c.shape[0] < m.text_len:
+                n_txt, txt_w = c.shape[0] + 1, float(m.text_len - c.shape[0])
+            legs.append((c, n_txt, txt_w))
+        img_shared = n_img > 0 and all(c is clip_feas[0] for c in clip_feas)
+        ctx_fresh = True
+        if self.cache_context:
+            ident = lambda c: None if c is None else (c.data_ptr(), c._version, tuple(c.shape))
+            key = (tuple(ident(c) for c in contexts), None if clip_feas is None else tuple(ident(c) for c in clip_feas), img_shared,
+                   self._packed_key, self.dedup_pad_keys)
+            ctx_fresh = key != self._batch_ctx_key
+            self._batch_ctx_key, self._batch_ctx_refs = key, (list(contexts), None if clip_feas is None else list(clip_feas))
+        else:
+            self._batch_ctx_key = None
+        cols = _round_up(max(n for _, n, _ in legs), 64)                   # one V^T row stride for all samples
+        kv_t = []
+        for s, (c, n_txt, _) in enumerate(legs):
+            ctx = self._buf(f"ctx_b{s}_{n_txt}", (n_txt, C), torch.bfloat16)
+            if ctx_fresh:
+                self._text_ctx(c, ctx)
+            kv_t.append(self._cross_kv(f"b{s}c{cols}", ctx, n_txt, self.P["wkv_c"], self.P["bkv_c"], self.P["nk_c"], ctx_fresh, cols=cols))
+        kv_i = []
+        for s in range(1 if img_shared else B if n_img else 0):
+            ctx = self._buf(f"ctx_bi{s}", (n_img, C), torch.bfloat16)
+            if ctx_fresh:
+                self._img_ctx(clip_feas[s], ctx)
+            kv_i.append(self._cross_kv(f"bi{s}", ctx, n_img, self.P["wkv_i"], self.P["bkv_i"], self.P["nk_i"], ctx_fresh))
+
+        self._blocks_batch(xs, B, L, pitch, tabs.view(nb, RT, 6, C), ridx, ropes, kv_t, [n for _, n, _ in legs], [w for _, _, w in legs],
+                           kv_i, n_img)
+        outs = []
+        for s, (R, _, row_idx, e, _) in enumerate(per):
+            ridx_new = row_idx[n_hist:] if row_idx is not None else None
+            outs.append(self._head(xs[s * pitch + n_hist:s * pitch + L], ridx_new, e, R, grid))
+        return outs
+
+    def _blocks_batch(self, xs, B, L, pitch, tab, ridx, rope, kv_t, n_txt, txt_w, kv_i, n_img):
+        """the blocks of forward_batch. xs fp32 [(B - 1) * pitch + L, C]: sample s at row s * pitch, in and out. The same kernel calls as
+        _blocks, on the stacked rows. kv_i: one (K, V^T) of the image tokens shared by all samples, or one per sample."""
+        m = self.model
+        C, H, Fd, eps = m.dim, m.num_heads, m.ffn_dim, m.eps
+        M = (B - 1) * pitch + L
+        # rows and V^T columns exist up to a whole key tile behind the last sample as well (zeros nobody writes): YUME_ATTN_KV_PADDED per sample
+        h = self._buf("h_b", (M, C), torch.bfloat16)
+        qk = self._buf("qk_b", (B * pitch, 2 * C), torch.bfloat16, zero=True)
+        vt = self._buf("vt_b", (C, B * pitch), torch.bfloat16, zero=True)
+        att = self._buf("att_b", (M, C), torch.bfloat16, zero=True)
+        ff = self._buf("ff_b", (M, Fd), torch.bfloat16)
+        ts = 6 * C
+        T = self._timed
+        # (the register-staged kernel of the cross-check mode has no segmented form: the 4-wave LDS-DMA kernel then)
+        seg_variant = 2 if self.attn_variant == 1 else self.attn_variant
+        if pitch > L:
+            for s in range(1, B):
+                att[s * pitch - (pitch - L):s * pitch].zero_()           # the gaps' attention rows: only a shared image branch adds to them
+        for i, d in enumerate(self.P["blocks"]):
+            tb = tab[i]
+            shift_sa, scale_sa, gate_sa = tb[:, 0], tb[:, 1], tb[:, 2]
+            shift_ff, scale_ff, gate_ff = tb[:, 3], tb[:, 4], tb[:, 5]
+            # --- self attention: one launch over the (sample, head) pairs
+            T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, ridx, True, h, 0, eps)
+            T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk[:M], EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+            T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M], C, 2, d["nqk"], self.qk_eps, rope)
+            T("attn_self", ops.attn_fwd_batch, qk[:M, :C], qk[:, C:], vt, att, B, L, pitch, L, pitch, H, variant=self.batch_attn_variant,
+              q_prescaled=self.q_prescale, kv_padded=True)
+            T("gemm_o", ops.gemm_bf16, att, d["wo"], d["bo"], xs, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ridx, variant=self.gemm_variant)
+            # --- cross attention
+            if "n3w" in d:
+                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
+            else:
+                ops.cast_bf16(xs, M, h)
+            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:M, :C], EPI_BF16, variant=self.gemm_variant)
+            T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M, :C], C, 1, d["nq_c"], self.qk_eps)
+            T("attn_cross", ops.attn_fwd_seg, qk[:M, :C], [kc[:, i * C:(i + 1) * C] for kc, _ in kv_t], [v[i * C:(i + 1) * C] for _, v in kv_t],
+              att, L, pitch, n_txt, H, variant=seg_variant, q_prescaled=self.q_prescale, kv_padded=True, last_key_weights=txt_w)
+            if len(kv_i) == 1:
+                T("attn_cross", ops.attn_fwd, qk[:M, :C], kv_i[0][0][:, i * C:(i + 1) * C], kv_i[0][1][i * C:(i + 1) * C], att, M, n_img, H,
+                  accumulate=True, variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
+            elif kv_i:
+                T("attn_cross", ops.attn_fwd_seg, qk[:M, :C], [kc[:, i * C:(i + 1) * C] for kc, _ in kv_i], [v[i * C:(i + 1) * C] for _, v in kv_i],
+                  att, L, pitch, [n_img] * B, H, accumulate=True, variant=seg_variant, q_prescaled=self.q_prescale, kv_padded=True)
+            T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
+            # --- FFN
+            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx, True, h, 0, eps)
+            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
+            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ridx, variant=self.gemm_variant)
 
     def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_last_weight=1.0):
         """Blocks + head on this rank's token chunk (sequence_parallel.py:121-152: chunk after the embeddings, gather

@@ -296,6 +296,60 @@ def attn_fwd_seg(q, ks, vts, out, Lq_seg, seg_pitch, Lks, H, scale=None, accumul
     return out
 
 
+_attn_batch_ws, _attn_batch_ws_bytes = {}, {}
+
+
+def attn_fwd_batch(q, k, vt, out, nseg, Lq_seg, q_pitch, Lk_seg, k_pitch, H, scale=None, accumulate=False, variant=0, use_workspace=True,
+                   q_prescaled=False, kv_padded=False):
+    """Batched self-attention (yume_attn_fwd_batch): nseg problems of one shape stacked in q / k / vt / out. Segment s = the rows
+    [s * q_pitch, s * q_pitch + Lq_seg) of q and out, the rows [s * k_pitch, s * k_pitch + Lk_seg) of k and the columns of vt from s * k_pitch
+    on; the pitch gaps are neither read for a result nor written. One launch of the persistent kernel over (segment, head) pairs where it
+    applies (variant 0 with both flags, Lk_seg >= 1536, Lq_seg >= 256; variant 8 insists, Lk_seg >= 512), otherwise one of the segmented
+    4-wave kernel (variant 2 insists). q_prescaled / kv_padded: as for attn_fwd, for every segment. The scratch for key-range pieces is kept
+    per (device, stream)."""
+    lib = _lib.load()
+    _dev(q, "q", torch.bfloat16)
+    _dev(k, "k", torch.bfloat16)
+    _dev(vt, "vt", torch.bfloat16)
+    _dev(out, "out", torch.bfloat16)
+    ensure_counters(q.device)
+    qp, ldq = _rows(q, "q")
+    kp, ldk = _rows(k, "k")
+    vp, ldv = _rows(vt, "vt")
+    op, ldo = _rows(out, "out")
+    rows = (nseg - 1) * q_pitch + Lq_seg
+    if nseg < 1 or q.shape[0] < rows or out.shape[0] < rows or q.shape[1] < H * 128 or out.shape[1] < H * 128:
+        raise RuntimeError(f"yume_amd.attn_fwd_batch: q {tuple(q.shape)} / out {tuple(out.shape)} do not hold {nseg} segments of {Lq_seg} rows "
+                           f"({q_pitch} apart) of {H} heads")
+    # every segment's keys must be there: with kv_padded up to the last whole tile (as attn_fwd checks), in k's STORAGE and in vt's columns
+    Lp = (Lk_seg + 63) // 64 * 64 if kv_padded else Lk_seg
+    need = k.storage_offset() + ((nseg - 1) * k_pitch + Lp - 1) * ldk + H * 128
+    have = k.untyped_storage().nbytes() // k.element_size()
+    if k.shape[0] < (nseg - 1) * k_pitch + Lk_seg or k.shape[1] < H * 128 or need > have:
+        raise RuntimeError(f"yume_amd.attn_fwd_batch: k {tuple(k.shape)} does not hold {nseg} segments of {Lp} keys ({k_pitch} apart) of {H} heads")
+    if vt.shape[0] < H * 128 or vt.shape[1] < (nseg - 1) * k_pitch + Lp:
+        raise RuntimeError(f"yume_amd.attn_fwd_batch: vt {tuple(vt.shape)} does not hold {nseg} segments of {Lp} key columns ({k_pitch} apart) "
+                           f"of {H} heads")
+    if scale is None:
+        scale = 1.0 / math.sqrt(128.0)
+    ws, nbytes = None, 0
+    if variant in (0, 8) and use_workspace:
+        key = (q.device.index, nseg, Lq_seg, Lk_seg, H)
+        nbytes = _attn_batch_ws_bytes.get(key)
+        if nbytes is None:
+            nbytes = _attn_batch_ws_bytes[key] = int(lib.yume_attn_batch_workspace_bytes(nseg, Lq_seg, Lk_seg, H))
+        if nbytes:
+            wkey = _ws_key(q)
+            ws = _attn_batch_ws.get(wkey)
+            if ws is None or ws.numel() < nbytes:
+                ws = _attn_batch_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
+    rc = lib.yume_attn_fwd_batch(qp, ldq, kp, ldk, vp, ldv, op, ldo, nseg, Lq_seg, q_pitch, Lk_seg, k_pitch, H, scale, 1 if accumulate else 0,
+                                 flags, _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+    _lib.check(rc, "yume_attn_fwd_batch")
+    return out
+
+
 def linear_smallm_f32(x, w, bias, out, in_act=0, out_act=0, add_table=None):
     lib = _lib.load()
     _dev(x, "x", torch.float32)

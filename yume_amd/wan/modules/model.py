@@ -125,3 +125,29 @@ class WanModel(_Base):
         return self.engine.forward_pair(u, t.reshape(-1)[:1], context[0], context_null[0],
                                         clip_fea=clip_fea[0] if clip_fea.dim() == 3 else clip_fea, packed=packed, lfz=latent_frame_zero,
                                         n_sel=(u.shape[1] - 9) if packed else None)
+
+    def forward_batch(self, x, t, context, seq_len, clip_fea=None, y=None, rand_num_img=None, enable_mask=False,
+                      latent_frame_zero=9, cache_sample=False, cache=None, return_cache=False, cache_list=None):
+        """B samples in one pass over their stacked rows (DiTEngine.forward_batch) — an added entry point beside the single-sample forward
+        (the reference's packed path is single-sample by construction, wan/modules/model.py:474-475,1011). Arguments as for forward with x
+        and y lists of B tensors, t [B], context a list of B prompts and clip_fea [B, 257, C] or ONE [257, C] shared by all samples (its
+        image keys are then projected once). Returns a list of B fp32 [C_out, F', H, W] — no cache: the block-residual cache
+        (cache_sample) is not implemented for the batch. Samples of different shapes are cut into runs of equal shape (at most 8 per run; a
+        run of one is a plain forward); the output order is the input order. A guided batch lists each sample twice, with its two prompts."""
+        assert clip_fea is not None and y is not None
+        if enable_mask:
+            raise NotImplementedError("enable_mask (MDT token masking) is a training-time path")
+        if cache_sample or cache is not None or return_cache or cache_list is not None:
+            raise NotImplementedError("forward_batch does not implement the block-residual cache (cache_sample, cache, return_cache, "
+                                      "cache_list); use forward per sample")
+        us = [torch.cat([u, v], dim=0) for u, v in zip(x, y)]
+        B = len(us)
+        t = t.reshape(-1)
+        if len(context) != B or t.shape[0] != B or (clip_fea.dim() == 3 and clip_fea.shape[0] != B):
+            raise RuntimeError(f"forward_batch: {B} samples, {len(context)} prompts, t of {t.shape[0]} entries, clip_fea {tuple(clip_fea.shape)}")
+        clips = [clip_fea[i] for i in range(B)] if clip_fea.dim() == 3 else [clip_fea] * B
+        packed = rand_num_img is not None and rand_num_img >= 0.4
+        kw = lambda i: dict(packed=packed, lfz=latent_frame_zero, n_sel=(us[i].shape[1] - 9) if packed else None)
+        return self._batched(us, lambda i: self.engine.forward_one(us[i], t[i:i + 1], context[i], clip_fea=clips[i], **kw(i)),
+                             lambda a, b: self.engine.forward_batch(us[a:b], [t[i:i + 1] for i in range(a, b)], list(context[a:b]),
+                                                                    clip_feas=clips[a:b], **kw(a)))

@@ -317,6 +317,38 @@ class WanModel(nn.Module):
             outs.append(self.engine.forward_one(u, ti, context[i], packed=bool(flag), lfz=latent_frame_zero))
         return outs
 
+    def _batched(self, us, one, many):
+        """forward_batch's runs: consecutive samples of one shape, at most 8 per run, go through many(i0, i1) (a run of one through
+        one(i)); the outputs come back in input order."""
+        outs, i0 = [], 0
+        while i0 < len(us):
+            i1 = i0 + 1
+            while i1 < len(us) and i1 - i0 < 8 and tuple(us[i1].shape) == tuple(us[i0].shape):
+                i1 += 1
+            outs += [one(i0)] if i1 - i0 == 1 else list(many(i0, i1))
+            i0 = i1
+        return outs
+
+    def forward_batch(self, x, t, context, seq_len, enable_mask=False, y=None, latent_frame_zero=8, input_ids=None, flag=True):
+        """B samples in one pass over their stacked rows (DiTEngine.forward_batch) — an added entry point: the reference's packed path is
+        single-sample by construction (wan/modules/model.py:474-475,1011) and `forward` keeps that contract. Arguments as for forward with
+        x (and y) lists of B tensors, t [B] (flag=True, the FramePack path: [B, seq_len], one per-token row per sample) and context a list
+        of B prompts. Returns a list of B fp32 tensors, each what forward returns for that sample alone. Samples of different shapes are cut
+        into runs of equal shape (at most 8 per run; a run of one is a plain forward); the output order is the input order. A guided batch
+        lists each sample twice, with its two prompts."""
+        if enable_mask:
+            raise NotImplementedError("enable_mask (MDT token masking) is a training-time path, not part of the "
+                                      "inference hot path this implementation covers")
+        if self.model_type == "i2v":
+            assert y is not None
+        us = list(x) if y is None else [torch.cat([u, v], dim=0) for u, v in zip(x, y)]
+        B = len(us)
+        if len(context) != B or t.shape[0] != B:
+            raise RuntimeError(f"forward_batch: {B} samples, {len(context)} prompts, t of shape {tuple(t.shape)} (one row per sample)")
+        kw = dict(packed=bool(flag), lfz=latent_frame_zero)
+        return self._batched(us, lambda i: self.engine.forward_one(us[i], t[i:i + 1], context[i], **kw),
+                             lambda a, b: self.engine.forward_batch(us[a:b], [t[i:i + 1] for i in range(a, b)], list(context[a:b]), **kw))
+
     def forward_cfg(self, x, t, context, context_null, seq_len, enable_mask=False, y=None, latent_frame_zero=8, input_ids=None, flag=True):
         """The two forwards of a classifier-free-guidance step in one pass (DiTEngine.forward_pair): x, t, y and the keyword arguments as
         for forward (one sample), context and context_null the conditional and the unconditional prompt. Returns (cond, uncond), each what
