@@ -11,6 +11,17 @@ bool w4_auto() {
     static const bool on = [] { const char* v = getenv("YUME_GEMM_W4"); return !v || atoi(v) != 0; }();
     return on;
 }
+// YUME_GEMM_LOG=1: one stderr line per kernel launch of this file, naming the kernel the call ran on (read once per process)
+bool gemm_log() {
+    static const bool on = [] { const char* v = getenv("YUME_GEMM_LOG"); return v && atoi(v) != 0; }();
+    return on;
+}
+void gemm_log_line(const char* kernel, int64_t M, int64_t N, int64_t K, int epi, int variant, int64_t lda, int64_t ldw, int64_t ldo, int64_t ldt,
+                   int64_t n_split, bool ws, int64_t batch) {
+    fprintf(stderr, "[gemm_bf16] %s M=%lld N=%lld K=%lld epi=%d variant=%d lda=%lld ldw=%lld ldo=%lld ldt=%lld n_split=%lld ws=%d batch=%lld\n", kernel,
+            (long long)M, (long long)N, (long long)K, epi, variant, (long long)lda, (long long)ldw, (long long)ldo, (long long)ldt, (long long)n_split,
+            ws ? 1 : 0, (long long)batch);
+}
 }  // namespace
 
 extern "C" int64_t yume_gemm_workspace_bytes(void) { return gemm_w4::sk_workspace_bytes(gemm_w4::SK_MAX_SLOTS); }
@@ -90,6 +101,9 @@ extern "C" int yume_gemm_bf16_ws(const void* A, int64_t lda, const void* W, int6
     // variant 3: the one-wave-per-SIMD 256x256 kernel where it applies (else as variant 2); variant 0 takes it wherever it took the 8-wave kernel
     const bool w4 = (variant == 3 || (variant == 0 && big && w4_auto())) && split_ok && gemm_w4::w4_applies(p, lda, epi) &&
                     (epi != YUME_EPI_BF16_SPLITT || (ldt % 8) == 0);
+    if (gemm_log())
+        gemm_log_line(epi == YUME_EPI_BF16_GEGLU ? "g256" : w4 ? (sk ? "w4+sk" : "w4") : big ? "g256" : "g128", M, N, K, epi, variant, lda, ldw, ldo, ldt,
+                      n_split, workspace != nullptr, 1);
 #define YUME_GO(E) (w4 ? gemm_w4::launch_w4(E, p, al, e, st, "gemm_bf16", variant == 0 ? workspace : nullptr, workspace_bytes) : big ? launch256<E>(p, al, e, st, "gemm_bf16") : launch<E>(p, al, e, st, "gemm_bf16"))
     switch (epi) {
         case YUME_EPI_BF16: return YUME_GO(YUME_EPI_BF16);
@@ -140,6 +154,7 @@ extern "C" int yume_gemm_bf16_batched(const void* A, int64_t lda, int64_t stride
     Epilogue e = {};
     e.out = out; e.ldo = ldo;
     hipStream_t st = (hipStream_t)stream;
+    if (gemm_log()) gemm_log_line("batched", M, N, K, epi, variant, lda, ldw, ldo, 0, 0, false, batch);
     if (epi == YUME_EPI_F32) return launch<YUME_EPI_F32>(p, al, e, st, "gemm_bf16_batched", (int)batch);
     return launch<YUME_EPI_BF16>(p, al, e, st, "gemm_bf16_batched", (int)batch);
 }
@@ -203,6 +218,9 @@ extern "C" int yume_gemm_bf16_splitk(const void* A, int64_t lda, const void* W, 
     const unsigned grid = (unsigned)((MN / 4 + 255) / 256 > 16384 ? 16384 : (MN / 4 + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
     const float* ws = (const float*)workspace;
+    if (gemm_log() && (epi == YUME_EPI_F32 || epi == YUME_EPI_RESID || epi == YUME_EPI_BF16 || epi == YUME_EPI_BF16_GELU || epi == YUME_EPI_BF16_GELU_ERF ||
+                       epi == YUME_EPI_BF16_GEGLU))
+        gemm_log_line("splitk_reduce", M, N, K, epi, 0, lda, ldw, ldo, 0, 0, true, splits);
 #define YUME_RED(E) hipLaunchKernelGGL((splitk_reduce_kernel<E>), dim3(grid), dim3(256), 0, st, ws, splits, MN, (int)N, bias, out, ldo)
     switch (epi) {
         case YUME_EPI_F32: YUME_RED(YUME_EPI_F32); break;
