@@ -162,6 +162,12 @@ int yume_rmsnorm_rope(void* buf, int64_t ld, int64_t T, int64_t C, int nparts,
  * viewed as [tokens*wperiod, C]. w: fp32 [wperiod, C]. */
 int yume_rmsnorm_rows_periodic(void* buf, int64_t ld, int64_t T, int64_t C, const float* w, int64_t wperiod, float eps,
                                void* stream);
+/* env YUME_NORM_LOG=1 (read once per process, like YUME_ATTN_LOG, YUME_GEMM_LOG and YUME_CONV_LOG): every kernel launch of
+ * yume_adaln_modulate, yume_rmsnorm_f32 (the T5 section below), yume_rmsnorm_rope and yume_rmsnorm_rows_periodic prints one stderr line
+ *   `[norm] <instance> T=.. C=.. nparts=.. out_kind=.. ldx=.. ldo=.. tab_stride=.. wperiod=.. rope=0|1 row_idx=0|1`
+ * <instance>: adaln2 (two rows per workgroup: C <= 3072, out_kind 0, T >= 1024), adaln<3|5|8> (C <= 3072 / 5120 / 8192), adaln_rms<3|5|8>
+ * (yume_rmsnorm_f32), rope2<2|3> (two rows: nparts*C/8 <= 512 / 768 vectors, wperiod 1, T >= 1024), rope<2|3|5|8> (<= 512 / 768 / 1280 /
+ * 2048 vectors). The in-place kernels print their one stride as ldx and ldo. tests/norm_cases.py holds one row per instance. */
 
 /* ---- exact-softmax attention forward (FlashAttention-style, head_dim 128) -----------------
  * replaces: wan23/modules/attention.py:24-130 flash_attention() -> flash_attn_varlen_func

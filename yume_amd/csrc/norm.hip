@@ -392,6 +392,20 @@ __global__ __launch_bounds__(NT) void rmsnorm_rope2_kernel(unsigned short* __res
     }
 }
 
+// YUME_NORM_LOG=1: one stderr line per kernel launch of this file, naming the kernel instance the call ran on (read once per process)
+bool norm_log() {
+    static const bool on = [] { const char* v = getenv("YUME_NORM_LOG"); return v && atoi(v) != 0; }();
+    return on;
+}
+void norm_log_line(const char* kernel, int maxv, int64_t T, int64_t C, int nparts, int out_kind, int64_t ldx, int64_t ldo, int64_t tab_stride,
+                   int wperiod, bool rope, bool row_idx) {
+    char name[32];
+    if (maxv > 0) snprintf(name, sizeof(name), "%s<%d>", kernel, maxv);
+    else snprintf(name, sizeof(name), "%s", kernel);
+    fprintf(stderr, "[norm] %s T=%lld C=%lld nparts=%d out_kind=%d ldx=%lld ldo=%lld tab_stride=%lld wperiod=%d rope=%d row_idx=%d\n", name,
+            (long long)T, (long long)C, nparts, out_kind, (long long)ldx, (long long)ldo, (long long)tab_stride, wperiod, rope ? 1 : 0, row_idx ? 1 : 0);
+}
+
 }  // namespace
 
 extern "C" int yume_adaln_modulate(const float* x, int64_t ldx, int64_t T, int64_t C, float eps, const float* mul,
@@ -406,7 +420,11 @@ extern "C" int yume_adaln_modulate(const float* x, int64_t ldx, int64_t T, int64
     const float one = add_one ? 1.f : 0.f;
     dim3 grid((unsigned)T), block(NT);
     static const bool two_rows = [] { const char* v = getenv("YUME_NORM_TWO_ROWS"); return !v || atoi(v) != 0; }();
-    if (two_rows && C <= NT * 4 * 3 && out_kind == 0 && T >= 1024 && T < (1ll << 31))
+    const bool use2 = two_rows && C <= NT * 4 * 3 && out_kind == 0 && T >= 1024 && T < (1ll << 31);
+    if (norm_log())
+        norm_log_line(use2 ? "adaln2" : "adaln", use2 ? 0 : C <= NT * 4 * 3 ? 3 : C <= NT * 4 * 5 ? 5 : 8, T, C, 1, out_kind, ldx, ldo, tab_stride, 1, false,
+                      row_idx != nullptr);
+    if (use2)
         hipLaunchKernelGGL(adaln2_kernel, dim3((unsigned)((T + 1) / 2)), block, 0, st, x, ldx, (int)T, (int)C, eps, mul, add, tab_stride, row_idx, one,
                            (unsigned short*)out, ldo);
     else if (C <= NT * 4 * 3)
@@ -427,6 +445,7 @@ extern "C" int yume_rmsnorm_f32(const float* x, int64_t ldx, int64_t T, int64_t 
     if (T == 0) return YUME_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)T), block(NT);
+    if (norm_log()) norm_log_line("adaln_rms", C <= NT * 4 * 3 ? 3 : C <= NT * 4 * 5 ? 5 : 8, T, C, 1, 0, ldx, ldo, 0, 1, false, false);
     if (C <= NT * 4 * 3)
         hipLaunchKernelGGL((adaln_kernel<3, true>), grid, block, 0, st, x, ldx, (int)C, eps, w, w, (int64_t)0, (const int32_t*)nullptr, 0.f, out, ldo, 0);
     else if (C <= NT * 4 * 5)
@@ -466,7 +485,11 @@ static int rmsnorm_rope_impl(void* buf, int64_t ld, int64_t T, int64_t C, int np
     const int64_t nvec = (C / 8) * nparts;
     dim3 grid((unsigned)T), block(NT);
     static const bool two_rows = [] { const char* v = getenv("YUME_NORM_TWO_ROWS"); return !v || atoi(v) != 0; }();
-    if (two_rows && wperiod == 1 && nvec <= NT * 3 && T >= 1024 && T < (1ll << 31)) {
+    const bool use2 = two_rows && wperiod == 1 && nvec <= NT * 3 && T >= 1024 && T < (1ll << 31);
+    if (norm_log())
+        norm_log_line(use2 ? "rope2" : "rope", nvec <= NT * 2 ? 2 : nvec <= NT * 3 ? 3 : nvec <= NT * 5 ? 5 : 8, T, C, nparts, 0, ld, ld, 0, wperiod,
+                      rope != nullptr, false);
+    if (use2) {
         const dim3 g2((unsigned)((T + 1) / 2));
         if (nvec <= NT * 2) hipLaunchKernelGGL(rmsnorm_rope2_kernel<2>, g2, block, 0, st, b, ld, (int)T, (int)C, nparts, w, eps, rope);
         else hipLaunchKernelGGL(rmsnorm_rope2_kernel<3>, g2, block, 0, st, b, ld, (int)T, (int)C, nparts, w, eps, rope);

@@ -83,6 +83,39 @@ def adaln_modulate(x, mul, add, tab_stride, row_idx, add_one, out, out_kind=0, e
     return out
 
 
+def rmsnorm_f32(x, w, out, eps=1e-6):
+    """out bf16 [T, C] = x * rsqrt(mean(x^2) + eps) * w (T5LayerNorm: no mean subtraction, no shift); x fp32 [T, C], w fp32 [C]."""
+    lib = _lib.load()
+    _dev(x, "x", torch.float32)
+    _dev(w, "w", torch.float32)
+    _dev(out, "out", torch.bfloat16)
+    xp, ldx = _rows(x, "x")
+    op, ldo = _rows(out, "out")
+    T, C = x.shape
+    if tuple(out.shape) != (T, C) or w.numel() != C or not w.is_contiguous():
+        raise RuntimeError(f"yume_amd.rmsnorm_f32: x {tuple(x.shape)}, w {tuple(w.shape)}, out {tuple(out.shape)} do not fit")
+    rc = lib.yume_rmsnorm_f32(xp, ldx, T, C, eps, w.data_ptr(), op, ldo, _stream())
+    _lib.check(rc, "yume_rmsnorm_f32")
+    return out
+
+
+def softmax_bias_rows(S, bias, P, n):
+    """P[h, i, :n] = softmax_j(S[h, i, j] + bias[h, j - i + n - 1]), P[h, i, n:] = 0 (the T5 attention rows, no scaling). S fp32 [H, n, >= n],
+    bias fp32 [H, >= 2n - 1], P bf16 [H, n, .] whose row stride ldp = P.stride(1), n <= ldp <= 1024, is zeroed up to; the last dim of each contiguous."""
+    lib = _lib.load()
+    _dev(S, "S", torch.float32)
+    _dev(bias, "bias", torch.float32)
+    _dev(P, "P", torch.bfloat16)
+    if S.dim() != 3 or P.dim() != 3 or bias.dim() != 2 or S.stride(2) != 1 or P.stride(2) != 1 or bias.stride(1) != 1:
+        raise RuntimeError("yume_amd.softmax_bias_rows: S and P must be 3-D, bias 2-D, each with a contiguous last dim")
+    H = S.shape[0]
+    if S.shape[1] != n or P.shape[:2] != (H, n) or bias.shape[0] != H:
+        raise RuntimeError(f"yume_amd.softmax_bias_rows: S {tuple(S.shape)}, bias {tuple(bias.shape)}, P {tuple(P.shape)} do not fit n={n}")
+    rc = lib.yume_softmax_bias_rows(S.data_ptr(), S.stride(1), S.stride(0), H, n, bias.data_ptr(), bias.stride(0), P.data_ptr(), P.stride(1), P.stride(0), _stream())
+    _lib.check(rc, "yume_softmax_bias_rows")
+    return P
+
+
 # scratch of the GEMM's stream-K tail (yume_gemm_bf16_ws): one zero-initialised buffer per (device, stream) — launches sharing it are ordered
 _gemm_ws = {}
 

@@ -201,24 +201,20 @@ class T5Engine:
         ff = self._buf("ff", (n, Dff), torch.bfloat16)
         tabs = self._bias_tables(n)
         for d, bias in zip(self.P["blocks"], tabs):
-            _lib.check(lib.yume_rmsnorm_f32(x.data_ptr(), C, n, C, m.blocks[0].norm1.eps, d["n1"].data_ptr(), h.data_ptr(), C, st),
-                       "yume_rmsnorm_f32")
+            ops.rmsnorm_f32(x, d["n1"], h, m.blocks[0].norm1.eps)
             ops.gemm_bf16(h, d["wqkv"], None, qk[:n], ops.EPI_BF16_SPLITT, out_t=vt, n_split=2 * Da)
             # S[h] = q_h . k_h^T (no scaling): A = q columns of head h, W = the k rows (k is [keys, d] already)
             _lib.check(lib.yume_gemm_bf16_batched(qk.data_ptr(), 2 * Da, hd, qk[:, Da:].data_ptr(), 2 * Da, hd, n, npad, hd,
                                                   ops.EPI_F32, S.data_ptr(), npad, n * npad, H, 0, st), "yume_gemm_bf16_batched")
-            _lib.check(lib.yume_softmax_bias_rows(S.data_ptr(), npad, n * npad, H, n, bias.data_ptr(), bias.shape[1],
-                                                  Pm.data_ptr(), npad, n * npad, st), "yume_softmax_bias_rows")
+            ops.softmax_bias_rows(S, bias, Pm, n)
             # att[:, head h] = P[h] . v_h : W = the K-major V^T rows of head h
             _lib.check(lib.yume_gemm_bf16_batched(Pm.data_ptr(), npad, n * npad, vt.data_ptr(), npad, hd * npad, n, hd, npad,
                                                   ops.EPI_BF16, att.data_ptr(), Da, hd, H, 0, st), "yume_gemm_bf16_batched")
             ops.gemm_small_m(att, d["wo"], None, x, ops.EPI_RESID)
-            _lib.check(lib.yume_rmsnorm_f32(x.data_ptr(), C, n, C, m.blocks[0].norm2.eps, d["n2"].data_ptr(), h.data_ptr(), C, st),
-                       "yume_rmsnorm_f32")
+            ops.rmsnorm_f32(x, d["n2"], h, m.blocks[0].norm2.eps)
             ops.gemm_small_m(h, d["wgeglu"], None, ff, EPI_BF16_GEGLU)          # split-K; falls back to the 256x256 GEGLU kernel
             ops.gemm_small_m(ff, d["w2"], None, x, ops.EPI_RESID)
-        _lib.check(lib.yume_rmsnorm_f32(x.data_ptr(), C, n, C, m.norm.eps, self.P["norm"].data_ptr(), h.data_ptr(), C, st),
-                   "yume_rmsnorm_f32")
+        ops.rmsnorm_f32(x, self.P["norm"], h, m.norm.eps)
         return h.float()
 
 
