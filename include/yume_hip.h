@@ -142,6 +142,32 @@ int yume_gemm_bf16_ws(const void* A, int64_t lda, const void* W, int64_t ldw, co
                       void* outT, int64_t ldt, int64_t n_split,
                       int variant, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- FP8 (OCP e4m3fn) FFN linears (r15; functions added, no argument list changed: ABI 9) ---------------------------------
+ * replaces (opt-in, DiTEngine.fp8_ffn): the two FFN linears of a block, wan23/modules/model.py:265-267,309-312.
+ *
+ * yume_quant_rows_e4m3: per-row absmax quantiser. x bf16 [R, K] (row stride ldx elements), q u8 [R, K] (row stride ldq bytes),
+ * scale fp32 [R]:
+ *     amax = max_k |x[r, k]|;  scale[r] = amax / 448.0f (one IEEE fp32 division; 1.0f for an all-zero row);
+ *     q[r, k] = e4m3_rne(clamp(x[r, k] / scale[r], +-448))          (clamped BEFORE the conversion: no byte is 0x7f / 0xff)
+ * x / scale is formed with a reciprocal: |q - x / scale| <= half an e4m3 ulp + 2^-20 |x / scale|. Bytes beyond K of a q row and rows
+ * beyond R are not written. Checks (YUME_EINVAL): K % 16 == 0, ldq % 16 == 0, ldx % 8 == 0, ldx >= K, ldq >= K, x and q 16-byte
+ * aligned. R == 0: YUME_OK, nothing is launched. The same call quantises activations [L, K] and weights [N, K] (one scale per channel).
+ *
+ * yume_gemm_f8:   acc[m, n] = sum_k Aq[m, k] * Wq[n, k]  (e4m3 x e4m3, fp32 sum);   y = acc * sa[m] * sw[n] + bias[n];  then `epi`:
+ *   YUME_EPI_BF16 / YUME_EPI_BF16_GELU (tanh) / YUME_EPI_F32 / YUME_EPI_RESID with out, ldo, gate, gate_stride, row_idx exactly as in
+ *   yume_gemm_bf16_ws; any other epilogue: YUME_EUNSUP.
+ * Aq u8 [M, K] (row stride lda bytes), Wq u8 [N, K] (ldw), sa fp32 [M], sw fp32 [N], bias fp32 [N] or NULL.
+ * Accuracy of the sum: v_mfma_scale_f32_16x16x128_f8f6f4 does not add its 128 products like an fp32 chain; measured on the bare
+ * instruction it errs by up to 3.2e-4 * sqrt(sum_k (a_k w_k)^2) per k-step, unbiased (profiles/r15_fp8_ffn.md) — far below the e4m3
+ * rounding of the operands, above the bf16 GEMM's fp32 sums. tests/gemm_f8_cases.py holds the call to twice that figure.
+ * Checks (YUME_EINVAL): K % 128 == 0, lda % 16 == 0, ldw % 16 == 0, N % 4 == 0, ldo % 4 == 0, Aq / Wq / out / sw / bias / gate 16-byte
+ * aligned, gate_stride % 4 == 0. M >= 1, N >= 1 otherwise arbitrary. One 256 x 256 output tile per workgroup, nothing is handed between
+ * workgroups; no workspace, no allocation, the caller's stream. */
+int yume_quant_rows_e4m3(const void* x, int64_t ldx, int64_t R, int64_t K, void* q, int64_t ldq, float* scale, void* stream);
+int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
+                 const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
+                 const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
+
 /* ---- RMSNorm over the hidden dim (+ optional 3D RoPE), in place, bf16 -----------------------
  * replaces: wan23/modules/model.py:121-137 (WanRMSNorm on q,k over the FULL hidden dim C),
  *           :38-118 (rope_apply: interleaved-pair complex multiply with the per-token table).

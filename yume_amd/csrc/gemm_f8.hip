@@ -1,0 +1,47 @@
+// gemm_f8.hip — C-ABI of the e4m3 x e4m3 GEMM with per-row / per-channel fp32 scales (kernel and epilogues: gemm_f8.hpp).
+// Roofline: MFMA (fp8 dense, 2x the bf16 rate per clock); algorithmic work 2*M*N*K flop per launch.
+#include "gemm_f8.hpp"
+
+using namespace gemm_core;
+
+namespace {
+// YUME_GEMM_LOG=1: one stderr line per launch, in the form of gemm_bf16.hip's (read once per process)
+bool f8_log() {
+    static const bool on = [] { const char* v = getenv("YUME_GEMM_LOG"); return v && atoi(v) != 0; }();
+    return on;
+}
+}  // namespace
+
+extern "C" int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw, const float* bias,
+                            int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo, const float* gate, int64_t gate_stride,
+                            const int32_t* row_idx, void* stream) {
+    if (epi != YUME_EPI_BF16 && epi != YUME_EPI_BF16_GELU && epi != YUME_EPI_F32 && epi != YUME_EPI_RESID) {
+        yume_set_error("gemm_f8: epilogue %d is not implemented (BF16, GELU, F32, RESID are)", epi);
+        return YUME_EUNSUP;
+    }
+    YUME_REQUIRE(Aq && Wq && sa && sw && out, "gemm_f8: NULL pointer");
+    YUME_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f8: empty problem M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+    YUME_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "gemm_f8: dimension too large");
+    YUME_REQUIRE((K % gemm_f8::F8_BK) == 0, "gemm_f8: K=%lld must be a multiple of %d", (long long)K, gemm_f8::F8_BK);
+    YUME_REQUIRE((N % 4) == 0, "gemm_f8: N=%lld must be a multiple of 4", (long long)N);
+    YUME_REQUIRE((lda % 16) == 0 && (ldw % 16) == 0 && lda >= K && ldw >= K, "gemm_f8: lda/ldw must be multiples of 16 (16-byte rows) and >= K");
+    YUME_REQUIRE((ldo % 4) == 0 && ldo >= N, "gemm_f8: ldo must be a multiple of 4 and >= N");
+    YUME_REQUIRE(((uintptr_t)Aq % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)sw % 16) == 0 &&
+                 ((uintptr_t)sa % 4) == 0 && (bias == nullptr || ((uintptr_t)bias % 16) == 0),
+                 "gemm_f8: Aq, Wq, out, sw and bias must be 16-byte aligned");
+    if (epi == YUME_EPI_RESID)
+        YUME_REQUIRE(gate == nullptr || ((gate_stride % 4) == 0 && ((uintptr_t)gate % 16) == 0), "gemm_f8: gate must be 16-byte aligned, gate_stride a multiple of 4");
+    Problem p = {};
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    gemm_f8::F8Args f;
+    f.A = (const unsigned char*)Aq; f.lda = lda; f.sa = sa;
+    f.W = (const unsigned char*)Wq; f.ldw = ldw; f.sw = sw;
+    Epilogue e = {};
+    e.bias = bias;
+    e.out = out; e.ldo = ldo;
+    e.gate = gate; e.gate_stride = gate_stride; e.row_idx = row_idx;
+    if (f8_log())
+        fprintf(stderr, "[gemm_f8] f8 M=%lld N=%lld K=%lld epi=%d lda=%lld ldw=%lld ldo=%lld\n", (long long)M, (long long)N, (long long)K, epi,
+                (long long)lda, (long long)ldw, (long long)ldo);
+    return gemm_f8::launch_f8(epi, p, f, e, (hipStream_t)stream);
+}

@@ -20,6 +20,7 @@ q|k bf16 [L, 2C]; V^T bf16 [C, Lpad] (K-major, per head 128 rows); modulation ta
 
 import math
 import os
+import sys
 
 import torch
 
@@ -82,6 +83,11 @@ class DiTEngine:
         # ops.attn_fwd launch per leg. Off by default = forward_pair as it was; env YUME_PAIR_SELF_BATCHED=1 turns it on (tools/batch_ab.py
         # measures both).
         self.pair_self_batched = os.environ.get("YUME_PAIR_SELF_BATCHED", "0") == "1"
+        # r15: the two FFN linears of every block whose dim and ffn_dim are multiples of 128 in OCP e4m3 with one fp32 scale per token row and
+        # per output channel (yume_quant_rows_e4m3 + yume_gemm_f8): weights quantised once at pack time, activations in front of each GEMM.
+        # QKV, o and the cross projections stay bf16. Off by default = the bf16 calls, bit for bit; env YUME_FP8_FFN=1 turns it on. Part of
+        # the pack key: flipping it re-packs.
+        self.fp8_ffn = os.environ.get("YUME_FP8_FFN", "0") == "1"
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -100,7 +106,7 @@ class DiTEngine:
     def _param_key(self):
         # walked once per forward: (storage address, in-place version, dtype) of every parameter — a load_state_dict, an
         # optimizer step or a .to(dtype) re-packs; cheap next to one forward (≈1 k tensors), and cached per forward call
-        return (self.q_prescale,) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
+        return (self.q_prescale, bool(self.fp8_ffn)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
 
     def _pack(self):
         m = self.model
@@ -166,6 +172,14 @@ class DiTEngine:
             }
             if getattr(b.norm3, "weight", None) is not None:
                 d["n3w"], d["n3b"] = f32(b.norm3.weight), f32(b.norm3.bias)
+            if self.fp8_ffn:
+                if C % 128 == 0 and m.ffn_dim % 128 == 0:
+                    for wk, qk_, sk_ in (("w1", "w1q", "s1"), ("w2", "w2q", "s2")):
+                        d[qk_] = torch.empty(d[wk].shape, dtype=torch.uint8, device=dev)
+                        d[sk_] = torch.empty(d[wk].shape[0], dtype=torch.float32, device=dev)
+                        ops.quant_rows_e4m3(d[wk], d[qk_], d[sk_])
+                elif os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
+                    sys.stderr.write(f"[fp8_ffn] block {len(blocks)} keeps bf16 FFN linears: dim={C} ffn_dim={m.ffn_dim} are not both multiples of 128\n")
             blocks.append(d)
         P["blocks"] = blocks
         # cross-attention K / V projections of ALL blocks as one weight: the conditioning tokens are the same for every block,
@@ -196,10 +210,13 @@ class DiTEngine:
             self._packed_key = key
 
     # ------------------------------------------------------------------ workspaces / per-clip tables
-    def _buf(self, name, shape, dtype, zero=False):
+    def _buf(self, name, shape, dtype, zero=False, grow_rows=False):
         """a workspace tensor, kept across calls while its shape holds. zero: zero-filled when (re)allocated — for buffers whose padding
-        (rows / columns no kernel writes) has to stay finite."""
+        (rows / columns no kernel writes) has to stay finite. grow_rows: a kept tensor with at least shape[0] rows (and the same other
+        dims) serves as its first shape[0] rows — for callers whose row count alternates (the trimmed last block beside the full ones)."""
         t = self._ws.get(name)
+        if grow_rows and t is not None and t.shape[0] >= shape[0] and tuple(t.shape[1:]) == tuple(shape[1:]) and t.dtype == dtype and t.device == self.dev:
+            return t[:shape[0]]
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev:
             t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.dev)
             self._ws[name] = t
@@ -385,10 +402,29 @@ class DiTEngine:
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
             T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, row_idx, True, h, 0, eps)
-            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
-            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=row_idx, variant=self.gemm_variant)
+            self._ffn(d, h, ff, xs, gate_ff, ts, row_idx)
             if cache is not None and cache[0] == "record" and i in cache[1]:
                 cache[2].append((xs - x_in).to(torch.bfloat16).unsqueeze(0))     # reference keeps [B, L, C] bf16
+
+    def _ffn(self, d, h, ff, xs, gate_ff, ts, row_idx):
+        """the block's FFN on h bf16 [n, C]: ff = gelu(h W1^T + b1), xs += (ff W2^T + b2) * gate. With fp8_ffn (and a block that qualified at
+        pack time) both linears run in e4m3: quant_rows(h) -> gemm_f8 (GELU -> ff bf16) -> quant_rows(ff) -> gemm_f8 (RESID into xs). The byte
+        and scale buffers are workspaces (nothing is allocated under a stream capture once they exist); the FFN is row-local, so sequence
+        parallelism and the row-offset views of the trimmed block need nothing."""
+        T = self._timed
+        if "w1q" not in d:
+            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
+            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=row_idx, variant=self.gemm_variant)
+            return
+        n = h.shape[0]
+        hq = self._buf("ffn_hq", (n, h.shape[1]), torch.uint8, grow_rows=True)
+        fq = self._buf("ffn_fq", (n, ff.shape[1]), torch.uint8, grow_rows=True)
+        sh = self._buf("ffn_sh", (n,), torch.float32, grow_rows=True)
+        sf = self._buf("ffn_sf", (n,), torch.float32, grow_rows=True)
+        T("quant_rows", ops.quant_rows_e4m3, h, hq, sh)
+        T("gemm_ffn0", ops.gemm_f8, hq, sh, d["w1q"], d["s1"], d["b1"], ff, EPI_BF16_GELU)
+        T("quant_rows", ops.quant_rows_e4m3, ff, fq, sf)
+        T("gemm_ffn2", ops.gemm_f8, fq, sf, d["w2q"], d["s2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=row_idx)
 
     def _trimmed_block(self, xs, L, s, d, i, tb, ts, row_idx, rope, eps, h, qk, vt, att, ff, kc_t, vct_t, ntxt, img, txt_last_weight=1.0,
                        txt_variant=0):
@@ -421,8 +457,7 @@ class DiTEngine:
               variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
         T("gemm_cross_o", ops.gemm_bf16, ao, d["wo_c"], d["bo_c"], xo, EPI_RESID, variant=self.gemm_variant)
         T("adaln", ops.adaln_modulate, xo, scale_ff, shift_ff, ts, ro, True, ho, 0, eps)
-        T("gemm_ffn0", ops.gemm_bf16, ho, d["w1"], d["b1"], fo, EPI_BF16_GELU, variant=self.gemm_variant)
-        T("gemm_ffn2", ops.gemm_bf16, fo, d["w2"], d["b2"], xo, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ro, variant=self.gemm_variant)
+        self._ffn(d, ho, fo, xo, gate_ff, ts, ro)
 
     # ------------------------------------------------------------------ one block through the engine (operator seam)
     @torch.no_grad()
@@ -726,8 +761,7 @@ class DiTEngine:
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
             T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx2, True, h, 0, eps)
-            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
-            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ridx2, variant=self.gemm_variant)
+            self._ffn(d, h, ff, xs, gate_ff, ts, ridx2)
 
     # ------------------------------------------------------------------ several samples in one pass
     @torch.no_grad()
@@ -896,8 +930,7 @@ class DiTEngine:
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
             T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx, True, h, 0, eps)
-            T("gemm_ffn0", ops.gemm_bf16, h, d["w1"], d["b1"], ff, EPI_BF16_GELU, variant=self.gemm_variant)
-            T("gemm_ffn2", ops.gemm_bf16, ff, d["w2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=ridx, variant=self.gemm_variant)
+            self._ffn(d, h, ff, xs, gate_ff, ts, ridx)
 
     def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_last_weight=1.0):
         """Blocks + head on this rank's token chunk (sequence_parallel.py:121-152: chunk after the embeddings, gather

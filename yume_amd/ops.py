@@ -163,6 +163,44 @@ def gemm_bf16(a, w, bias, out, epi=EPI_BF16, gate=None, gate_stride=0, row_idx=N
     return out
 
 
+def quant_rows_e4m3(x, q, scale):
+    """q u8 [R, K] = e4m3(x / scale[r]) with scale[r] = max|x[r]| / 448 (1 for a zero row); x bf16 [R, K], scale fp32 [R] (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(x, "x", torch.bfloat16)
+    _dev(q, "q", torch.uint8)
+    _dev(scale, "scale", torch.float32)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    R, K = x.shape
+    if tuple(q.shape) != (R, K) or scale.dim() != 1 or scale.numel() != R or not scale.is_contiguous():
+        raise RuntimeError(f"yume_amd.quant_rows_e4m3: x {tuple(x.shape)}, q {tuple(q.shape)}, scale {tuple(scale.shape)} do not fit")
+    rc = lib.yume_quant_rows_e4m3(xp, ldx, R, K, qp, ldq, scale.data_ptr(), _stream())
+    _lib.check(rc, "yume_quant_rows_e4m3")
+    return q, scale
+
+
+def gemm_f8(aq, sa, wq, sw, bias, out, epi=EPI_BF16, gate=None, gate_stride=0, row_idx=None):
+    """acc = aq @ wq.T (e4m3 bytes: aq u8 [M,K], wq u8 [N,K]); y = acc * sa[m] * sw[n] + bias; epilogue `epi` as gemm_bf16 (BF16, GELU, F32, RESID)."""
+    lib = _lib.load()
+    _dev(aq, "aq", torch.uint8)
+    _dev(wq, "wq", torch.uint8)
+    _dev(sa, "sa", torch.float32)
+    _dev(sw, "sw", torch.float32)
+    ap, lda = _rows(aq, "aq")
+    wp, ldw = _rows(wq, "wq")
+    M, K = aq.shape
+    N, K2 = wq.shape
+    if K != K2:
+        raise RuntimeError(f"yume_amd.gemm_f8: K mismatch {K} vs {K2}")
+    if sa.dim() != 1 or sa.numel() != M or not sa.is_contiguous() or sw.dim() != 1 or sw.numel() != N or not sw.is_contiguous():
+        raise RuntimeError(f"yume_amd.gemm_f8: scales sa {tuple(sa.shape)}, sw {tuple(sw.shape)} do not fit M={M}, N={N}")
+    op, ldo = _rows(out, "out")
+    rc = lib.yume_gemm_f8(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, epi, op, ldo, _ptr(gate), gate_stride,
+                          _ptr(row_idx), _stream())
+    _lib.check(rc, "yume_gemm_f8")
+    return out
+
+
 # Scratch buffers of the split-K GEMM and the attention key-range split are keyed by (device, stream): two callers on
 # different HIP streams of one device (a VAE decode overlapped with the next chunk's denoise, say) never share partials.
 _splitk_ws = {}
