@@ -117,7 +117,8 @@ enum {
     YUME_EPI_RESID = 3,
     YUME_EPI_BF16_SPLITT = 4,
     YUME_EPI_BF16_GELU_ERF = 5,
-    YUME_EPI_BF16_GEGLU = 6      /* see the T5 section below */
+    YUME_EPI_BF16_GEGLU = 6,     /* see the T5 section below */
+    YUME_EPI_MX_GELU = 7         /* yume_gemm_f8_mxout only: e4m3 bytes + one E8M0 scale byte per 32 columns (the FP8 FFN section) */
 };
 int yume_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
                    int64_t M, int64_t N, int64_t K, int epi,
@@ -167,6 +168,36 @@ int yume_quant_rows_e4m3(const void* x, int64_t ldx, int64_t R, int64_t K, void*
 int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
                  const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
                  const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
+
+/* ---- FP8 FFN without quantiser passes (r16; functions added, no argument list changed: ABI 9) ------------------------------
+ * yume_adaln_modulate_e4m3: yume_adaln_modulate(..., out_kind = 0) followed by yume_quant_rows_e4m3 on its bf16 output, in one
+ * kernel and without the bf16 row: the modulated value is rounded to bf16, the row amax of those values gives scale[t] = amax / 448
+ * (1 for a zero row), the bytes are the quantiser's. q u8 [T, C] (row stride ldq bytes) and scale fp32 [T] equal the two-call
+ * composite bit for bit. Checks (YUME_EINVAL): C % 16 == 0, C <= 8192, ldq % 16 == 0, ldq >= C, ldx % 4 == 0, tab_stride % 4 == 0,
+ * q 16-byte aligned. Bytes beyond C of a q row and rows beyond T are not written. T == 0: YUME_OK, nothing is launched. */
+int yume_adaln_modulate_e4m3(const float* x, int64_t ldx, int64_t T, int64_t C, float eps, const float* mul,
+                             const float* add, int64_t tab_stride, const int32_t* row_idx, int add_one,
+                             void* q, int64_t ldq, float* scale, void* stream);
+/* The OCP MX pair between ffn.0 and ffn.2: e4m3 bytes with one E8M0 scale byte (2^(byte - 127)) per row and 32 consecutive columns.
+ *
+ * yume_gemm_f8_mxout (the producer; epi must be YUME_EPI_MX_GELU, anything else YUME_EUNSUP): yume_gemm_f8's operands and sum;
+ *     v = gelu_tanh(acc * sa[m] * sw[n] + bias[n]) in fp32; per row and block of 32 columns amax = max |v|, e = the smallest integer
+ *     with amax <= 448 * 2^e clamped to [-127, 127] (taken from the fp32 bits; 0 for an all-zero block), eo[m, n / 32] = e + 127,
+ *     out[m, n] = e4m3_rne(clamp(v * 2^-e, +-448)).  out u8 [M, N] (row stride ldo bytes), eo u8 [M, N / 32] (row stride ldeo).
+ *     Checks: those of yume_gemm_f8 and N % 32 == 0, ldeo >= N / 32. Rows beyond M, bytes beyond N and scale bytes beyond N / 32 are
+ *     not written.
+ * yume_gemm_f8_mx (the consumer): acc[m, n] = sum_b 2^(ea[m, b] - 127) * sum_{k in block b} Aq[m, k] * Wq[n, k], the block scales
+ *     applied by v_mfma_scale_f32_16x16x128_f8f6f4 itself (scale map: profiles/r16_fp8_ffn_fused.md); y = acc * sw[n] + bias[n]; then
+ *     YUME_EPI_F32 or YUME_EPI_RESID as in yume_gemm_f8 (any other epilogue: YUME_EUNSUP). ea u8 [M, K / 32], row stride ldea with
+ *     ldea % 16 == 0 and ldea >= K / 32: the kernel reads a row's scale bytes in whole 16-byte groups, so up to 15 bytes behind K / 32
+ *     inside the pitch are read (never used). Other checks as yume_gemm_f8. Accuracy of the sum with unequal block scales: measured
+ *     3.8e-4 * sqrt(sum_k (2^e a_k w_k)^2) at worst; tests/gemm_f8_mx_cases.py holds the call to twice that. */
+int yume_gemm_f8_mxout(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
+                       const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
+                       void* eo, int64_t ldeo, void* stream);
+int yume_gemm_f8_mx(const void* Aq, int64_t lda, const void* ea, int64_t ldea, const void* Wq, int64_t ldw, const float* sw,
+                    const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
+                    const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
 
 /* ---- RMSNorm over the hidden dim (+ optional 3D RoPE), in place, bf16 -----------------------
  * replaces: wan23/modules/model.py:121-137 (WanRMSNorm on q,k over the FULL hidden dim C),

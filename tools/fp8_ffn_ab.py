@@ -4,12 +4,14 @@
      1. op level, at the FFN shape of the model: M tokens, dim <-> ffn_dim
            bf16      gemm_bf16 ffn.0 (GELU) + gemm_bf16 ffn.2 (RESID, gated)
            fp8       quant_rows(h) + gemm_f8 ffn.0 (GELU) + quant_rows(ff) + gemm_f8 ffn.2 (RESID, gated)
-        and each of the six pieces on its own. The bf16 side is ops.gemm_bf16 with variant 0, which is what the engine passes
+           fused     (r16, DiTEngine.fp8_ffn_fused) gemm_f8 ffn.0 (MX_GELU: e4m3 + E8M0 scale bytes out) + gemm_f8_mx ffn.2 (RESID, gated)
+        each leg WITH its FFN adaLN launch in front (adaln_modulate for bf16 and fp8, adaln_modulate_e4m3 for fused: the fused adaLN is
+        paid for), and each of the pieces on its own. The bf16 side is ops.gemm_bf16 with variant 0, which is what the engine passes
         (DiTEngine.gemm_variant = 0): the routes the step runs — gemm_w4 + the row-split remainder for ffn.0, gemm_w4 with the split-K
         tail (ops.py hands over its workspace) for ffn.2.
            --model 5b    M = 9460, 3072 <-> 14336        --model 14b   M = 27810 (--rows overrides), 5120 <-> 13824
-     2. --step: the whole --layers-block step (5b: bench.py's flagship workload, 30 blocks) with the option off / on, and the relative
-        difference of the two outputs.
+     2. --step: the whole --layers-block step (5b: bench.py's flagship workload, 30 blocks) with the option off / on / on with the fused
+        form, and the relative differences of the outputs.
    Prints means and spreads, TFLOP/s of the GEMM pieces, GB/s of the quantiser passes, and the box's calibration (yume_calibrate_mfma).
    A tool, not a test."""
 import argparse
@@ -54,8 +56,13 @@ s1, s2 = torch.empty(Fd, dtype=torch.float32, device=dev), torch.empty(C, dtype=
 ops.quant_rows_e4m3(w1, w1q, s1)
 ops.quant_rows_e4m3(w2, w2q, s2)
 gate = tab[:, 2]
+fe = torch.empty(M, (Fd // 32 + 15) // 16 * 16, dtype=torch.uint8, device=dev)[:, :Fd // 32]
 
 pieces = {
+    "adaln": lambda: ops.adaln_modulate(xs, tab[:, 4], tab[:, 3], 6 * C, ridx, True, h, 0),
+    "adaln_e4m3": lambda: ops.adaln_modulate_e4m3(xs, tab[:, 4], tab[:, 3], 6 * C, ridx, True, hq, sh),
+    "mx_ffn0": lambda: ops.gemm_f8_mxout(hq, sh, w1q, s1, b1, fq, fe),
+    "mx_ffn2": lambda: ops.gemm_f8_mx(fq, fe, w2q, s2, b2, xs, ops.EPI_RESID, gate=gate, gate_stride=6 * C, row_idx=ridx),
     "bf16_ffn0": lambda: ops.gemm_bf16(h, w1, b1, ff, ops.EPI_BF16_GELU),
     "bf16_ffn2": lambda: ops.gemm_bf16(ff, w2, b2, xs, ops.EPI_RESID, gate=gate, gate_stride=6 * C, row_idx=ridx),
     "quant_h": lambda: ops.quant_rows_e4m3(h, hq, sh),
@@ -64,8 +71,9 @@ pieces = {
     "f8_ffn2": lambda: ops.gemm_f8(fq, sf, w2q, s2, b2, xs, ops.EPI_RESID, gate=gate, gate_stride=6 * C, row_idx=ridx),
 }
 forms = dict(pieces)
-forms["bf16"] = lambda: (pieces["bf16_ffn0"](), pieces["bf16_ffn2"]())
-forms["fp8"] = lambda: (pieces["quant_h"](), pieces["f8_ffn0"](), pieces["quant_ff"](), pieces["f8_ffn2"]())
+forms["bf16"] = lambda: (pieces["adaln"](), pieces["bf16_ffn0"](), pieces["bf16_ffn2"]())
+forms["fp8"] = lambda: (pieces["adaln"](), pieces["quant_h"](), pieces["f8_ffn0"](), pieces["quant_ff"](), pieces["f8_ffn2"]())
+forms["fused"] = lambda: (pieces["adaln_e4m3"](), pieces["mx_ffn0"](), pieces["mx_ffn2"]())
 
 cal = calibrate.mfma_sustained(dev)
 REPS = 4                                     # launches per timed bracket (an event pair costs a few microseconds)
@@ -107,6 +115,9 @@ for name, ts in times.items():
         extra = f"   {res[name]['gb_per_s']:7.1f} GB/s (2 B read + 1 B written per element; the second read of a row comes from the L2)"
     print(f"{name:10s} mean {mean:8.4f} ms   spread {min(ts):8.4f} .. {max(ts):8.4f} ms{extra}")
 print(f"fp8 - bf16: {res['fp8']['mean_ms'] - res['bf16']['mean_ms']:+.4f} ms per block ({(res['fp8']['mean_ms'] / res['bf16']['mean_ms'] - 1) * 100:+.1f} %)")
+print(f"fused - bf16: {res['fused']['mean_ms'] - res['bf16']['mean_ms']:+.4f} ms per block ({(res['fused']['mean_ms'] / res['bf16']['mean_ms'] - 1) * 100:+.1f} %); "
+      f"fused - fp8: {res['fused']['mean_ms'] - res['fp8']['mean_ms']:+.4f} ms ({(res['fused']['mean_ms'] / res['fp8']['mean_ms'] - 1) * 100:+.1f} %) "
+      "(every leg with its FFN adaLN launch)")
 print(f"calibration: {cal['tflops']:.0f} TFLOP/s sustained MFMA, {cal['clock_ghz']:.3f} GHz")
 
 if args.step:
@@ -120,7 +131,7 @@ if args.step:
         plan = framepack.pack_plan(F, H, W, lfz, F - 9)
     if args.layers:
         cfg["num_layers"] = args.layers
-    def build(option):
+    def build(option, fused=False):
         with torch.device(dev):
             model = WanModel(**cfg)
             if args.model == "14b":
@@ -128,10 +139,11 @@ if args.step:
         synth.randomize_module_(model, seed=0)
         model = model.to(torch.bfloat16).eval().requires_grad_(False)
         model.engine.fp8_ffn = option
+        model.engine.fp8_ffn_fused = fused
         return model
 
     # two models with the same weights, one per setting: toggling the option of ONE engine would re-pack (and re-quantise) inside the timed call
-    models = {False: build(False), True: build(True)}
+    models = {False: build(False), True: build(True), "fused": build(True, True)}
     L = plan.seq_len
     ctx = rnd(77, 4096)
     if args.model == "5b":
@@ -147,7 +159,7 @@ if args.step:
     def with_option(on):
         return lambda: step(on)
 
-    sforms = {"step_off": with_option(False), "step_on": with_option(True)}
+    sforms = {"step_off": with_option(False), "step_on": with_option(True), "step_fused": with_option("fused")}
     for _ in range(args.warmup):
         for fn in sforms.values():
             fn()
@@ -170,4 +182,9 @@ if args.step:
     res["rel_l2_on_vs_off"] = rel
     print(f"step_on - step_off: {res['step_on']['mean_ms'] - res['step_off']['mean_ms']:+.2f} ms "
           f"({(res['step_on']['mean_ms'] / res['step_off']['mean_ms'] - 1) * 100:+.2f} %); rel-L2 of the outputs on against off {rel:.3e}")
+    relf = ((outs["step_fused"].double() - outs["step_off"].double()).norm() / outs["step_off"].double().norm()).item()
+    res["rel_l2_fused_vs_off"] = relf
+    print(f"step_fused - step_off: {res['step_fused']['mean_ms'] - res['step_off']['mean_ms']:+.2f} ms "
+          f"({(res['step_fused']['mean_ms'] / res['step_off']['mean_ms'] - 1) * 100:+.2f} %); step_fused - step_on: "
+          f"{res['step_fused']['mean_ms'] - res['step_on']['mean_ms']:+.2f} ms; rel-L2 of the outputs fused against off {relf:.3e}")
 print(json.dumps(res), flush=True)

@@ -6,6 +6,8 @@
 // Per trial: A [16][128], B [16][128] random e4m3 (every finite byte equally likely: magnitudes 2^-9 .. 448), C = 0 or random fp32.
 // Operand map used (the pattern rows of tests/gemm_f8_cases.py establish it): lane l holds row l & 15, bytes k = 32 (l >> 4) .. + 31;
 // result register r of lane l = D[row of the FIRST operand 4 (l >> 4) + r][row of the SECOND operand l & 15].
+// (r16: that k assignment is one of many this probe and the pattern rows cannot tell apart — any one gives the same sums when both operands
+// use it. The instruction's own k order, which the scale blocks follow, is in mfma_f8_scale_map.hip beside this file.)
 // Prints the worst |D - fp64| / sqrt(Q), the worst |D - fp64| / (2^-24 (sum_k |a_k b_k| + |c|)), how many results are exact, and the mean
 // absolute and signed error (is the sum biased towards zero?).
 #include <hip/hip_runtime.h>

@@ -22,11 +22,14 @@ SIGNATURES = {
     "yume_counter_workspace_init": [_P, _L, _P],
     "yume_calibrate_mfma": [_L, _L, _P, _P, _P],
     "yume_adaln_modulate": [_P, _L, _L, _L, _F, _P, _P, _L, _P, _I, _P, _L, _I, _P],
+    "yume_adaln_modulate_e4m3": [_P, _L, _L, _L, _F, _P, _P, _L, _P, _I, _P, _L, _P, _P],
     "yume_gemm_bf16": [_P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P, _L, _L, _I, _P],
     "yume_gemm_workspace_bytes": [],
     "yume_gemm_bf16_ws": [_P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P, _L, _L, _I, _P, _L, _P],
     "yume_quant_rows_e4m3": [_P, _L, _L, _L, _P, _L, _P, _P],
     "yume_gemm_f8": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P],
+    "yume_gemm_f8_mxout": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P],
+    "yume_gemm_f8_mx": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P],
     "yume_rmsnorm_f32": [_P, _L, _L, _L, _F, _P, _P, _L, _P],
     "yume_gemm_bf16_batched": [_P, _L, _L, _P, _L, _L, _L, _L, _L, _I, _P, _L, _L, _L, _I, _P],
     "yume_gemm_splitk_workspace_bytes": [_L, _L, _I],

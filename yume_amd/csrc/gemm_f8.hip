@@ -33,7 +33,7 @@ extern "C" int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const 
         YUME_REQUIRE(gate == nullptr || ((gate_stride % 4) == 0 && ((uintptr_t)gate % 16) == 0), "gemm_f8: gate must be 16-byte aligned, gate_stride a multiple of 4");
     Problem p = {};
     p.M = (int)M; p.N = (int)N; p.K = (int)K;
-    gemm_f8::F8Args f;
+    gemm_f8::F8Args f = {};
     f.A = (const unsigned char*)Aq; f.lda = lda; f.sa = sa;
     f.W = (const unsigned char*)Wq; f.ldw = ldw; f.sw = sw;
     Epilogue e = {};
@@ -44,4 +44,75 @@ extern "C" int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const 
         fprintf(stderr, "[gemm_f8] f8 M=%lld N=%lld K=%lld epi=%d lda=%lld ldw=%lld ldo=%lld\n", (long long)M, (long long)N, (long long)K, epi,
                 (long long)lda, (long long)ldw, (long long)ldo);
     return gemm_f8::launch_f8(epi, p, f, e, (hipStream_t)stream);
+}
+
+// (r16) the producer: yume_gemm_f8's operands, epi = YUME_EPI_MX_GELU, out = e4m3 bytes [M, N] (ldo bytes), eo = E8M0 scale bytes [M, N / 32]
+extern "C" int yume_gemm_f8_mxout(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw, const float* bias,
+                                  int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo, void* eo, int64_t ldeo, void* stream) {
+    if (epi != YUME_EPI_MX_GELU) {
+        yume_set_error("gemm_f8_mxout: epilogue %d is not implemented (MX_GELU is)", epi);
+        return YUME_EUNSUP;
+    }
+    YUME_REQUIRE(Aq && Wq && sa && sw && out && eo, "gemm_f8_mxout: NULL pointer");
+    YUME_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f8_mxout: empty problem M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+    YUME_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "gemm_f8_mxout: dimension too large");
+    YUME_REQUIRE((K % gemm_f8::F8_BK) == 0, "gemm_f8_mxout: K=%lld must be a multiple of %d", (long long)K, gemm_f8::F8_BK);
+    YUME_REQUIRE((N % 32) == 0, "gemm_f8_mxout: N=%lld must be a multiple of 32 (one scale byte per 32 columns)", (long long)N);
+    YUME_REQUIRE((lda % 16) == 0 && (ldw % 16) == 0 && lda >= K && ldw >= K, "gemm_f8_mxout: lda/ldw must be multiples of 16 (16-byte rows) and >= K");
+    YUME_REQUIRE((ldo % 4) == 0 && ldo >= N, "gemm_f8_mxout: ldo must be a multiple of 4 and >= N");
+    YUME_REQUIRE(ldeo >= N / 32, "gemm_f8_mxout: ldeo=%lld must be >= N / 32", (long long)ldeo);
+    YUME_REQUIRE(((uintptr_t)Aq % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)sw % 16) == 0 &&
+                 ((uintptr_t)sa % 4) == 0 && (bias == nullptr || ((uintptr_t)bias % 16) == 0),
+                 "gemm_f8_mxout: Aq, Wq, out, sw and bias must be 16-byte aligned");
+    Problem p = {};
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    gemm_f8::F8Args f = {};
+    f.A = (const unsigned char*)Aq; f.lda = lda; f.sa = sa;
+    f.W = (const unsigned char*)Wq; f.ldw = ldw; f.sw = sw;
+    f.eo = (unsigned char*)eo; f.ldeo = ldeo;
+    Epilogue e = {};
+    e.bias = bias;
+    e.out = out; e.ldo = ldo;
+    if (f8_log())
+        fprintf(stderr, "[gemm_f8] f8 M=%lld N=%lld K=%lld epi=%d lda=%lld ldw=%lld ldo=%lld ldeo=%lld\n", (long long)M, (long long)N, (long long)K, epi,
+                (long long)lda, (long long)ldw, (long long)ldo, (long long)ldeo);
+    return gemm_f8::launch_f8(epi, p, f, e, (hipStream_t)stream);
+}
+
+// (r16) the consumer: the activations' scales are E8M0 bytes per row and 32 k (ea, ldea) and act inside the instruction
+extern "C" int yume_gemm_f8_mx(const void* Aq, int64_t lda, const void* ea, int64_t ldea, const void* Wq, int64_t ldw, const float* sw,
+                               const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo, const float* gate,
+                               int64_t gate_stride, const int32_t* row_idx, void* stream) {
+    if (epi != YUME_EPI_F32 && epi != YUME_EPI_RESID) {
+        yume_set_error("gemm_f8_mx: epilogue %d is not implemented (F32, RESID are)", epi);
+        return YUME_EUNSUP;
+    }
+    YUME_REQUIRE(Aq && Wq && ea && sw && out, "gemm_f8_mx: NULL pointer");
+    YUME_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f8_mx: empty problem M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+    YUME_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "gemm_f8_mx: dimension too large");
+    YUME_REQUIRE((K % gemm_f8::F8_BK) == 0, "gemm_f8_mx: K=%lld must be a multiple of %d", (long long)K, gemm_f8::F8_BK);
+    YUME_REQUIRE((N % 4) == 0, "gemm_f8_mx: N=%lld must be a multiple of 4", (long long)N);
+    YUME_REQUIRE((lda % 16) == 0 && (ldw % 16) == 0 && lda >= K && ldw >= K, "gemm_f8_mx: lda/ldw must be multiples of 16 (16-byte rows) and >= K");
+    // the kernel reads a row's scale bytes in whole 16-byte groups: the pitch must hold them
+    YUME_REQUIRE((ldea % 16) == 0 && ldea >= K / 32, "gemm_f8_mx: ldea=%lld must be a multiple of 16 and >= K / 32", (long long)ldea);
+    YUME_REQUIRE((ldo % 4) == 0 && ldo >= N, "gemm_f8_mx: ldo must be a multiple of 4 and >= N");
+    YUME_REQUIRE(((uintptr_t)Aq % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)sw % 16) == 0 &&
+                 ((uintptr_t)ea % 16) == 0 && (bias == nullptr || ((uintptr_t)bias % 16) == 0),
+                 "gemm_f8_mx: Aq, ea, Wq, out, sw and bias must be 16-byte aligned");
+    if (epi == YUME_EPI_RESID)
+        YUME_REQUIRE(gate == nullptr || ((gate_stride % 4) == 0 && ((uintptr_t)gate % 16) == 0), "gemm_f8_mx: gate must be 16-byte aligned, gate_stride a multiple of 4");
+    Problem p = {};
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    gemm_f8::F8Args f = {};
+    f.A = (const unsigned char*)Aq; f.lda = lda;
+    f.W = (const unsigned char*)Wq; f.ldw = ldw; f.sw = sw;
+    f.ea = (const unsigned char*)ea; f.ldea = ldea;
+    Epilogue e = {};
+    e.bias = bias;
+    e.out = out; e.ldo = ldo;
+    e.gate = gate; e.gate_stride = gate_stride; e.row_idx = row_idx;
+    if (f8_log())
+        fprintf(stderr, "[gemm_f8] mx M=%lld N=%lld K=%lld epi=%d lda=%lld ldea=%lld ldw=%lld ldo=%lld\n", (long long)M, (long long)N, (long long)K, epi,
+                (long long)lda, (long long)ldea, (long long)ldw, (long long)ldo);
+    return gemm_f8::launch_f8_mx(epi, p, f, e, (hipStream_t)stream);
 }

@@ -217,6 +217,249 @@ __global__ __launch_bounds__(NT) void adaln2_kernel(const float* __restrict__ x,
     }
 }
 
+// ---- (r16) adaLN straight to e4m3: yume_quant_rows_e4m3 (quant_rows.hip) applied to the bf16 row the kernels above would have stored,
+// without the store and the re-read. The workgroup holds the whole row: the modulated values are rounded to bf16 (the same pack), the row
+// amax of THOSE values goes through one more block reduction (a max: exact, order-free), and scale / pre / inv / clamp / convert are the
+// quantiser's expressions word for word, so bytes and scales equal the two-call composite bit for bit (tests/test_norm_e4m3_gpu.py).
+constexpr float E4M3_MAX = 448.0f;
+
+__device__ __forceinline__ float block_max(float v, float* red /*[8]*/) {
+    v = wave_max(v);
+    const int wid = threadIdx.x >> 6;
+    __syncthreads();  // protect `red` against the previous use
+    if ((threadIdx.x & 63) == 0) red[wid] = v;
+    __syncthreads();
+    float t = red[0];
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) t = fmaxf(t, red[i]);
+    return t;
+}
+
+__device__ __forceinline__ void block_max2(float& a, float& b, float* red /*[16]*/) {
+    a = wave_max(a);
+    b = wave_max(b);
+    const int wid = threadIdx.x >> 6;
+    __syncthreads();  // protect `red` against the previous use
+    if ((threadIdx.x & 63) == 0) { red[wid] = a; red[8 + wid] = b; }
+    __syncthreads();
+    float ta = red[0], tb = red[8];
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) { ta = fmaxf(ta, red[i]); tb = fmaxf(tb, red[8 + i]); }
+    a = ta;
+    b = tb;
+}
+
+// four bf16 (two packed dwords, element 0 in the low half as pack_bf16x2 leaves them)
+__device__ __forceinline__ float absmax4(u32x2 h, float m) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        m = fmaxf(m, fabsf(__uint_as_float(h[q] << 16)));
+        m = fmaxf(m, fabsf(__uint_as_float(h[q] & 0xffff0000u)));
+    }
+    return m;
+}
+
+// four bf16 -> four e4m3 bytes: one half of quant_rows.hip's quant8
+__device__ __forceinline__ unsigned quant4(u32x2 h, float pre, float inv) {
+    float f[4];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        f[2 * q] = __uint_as_float(h[q] << 16);
+        f[2 * q + 1] = __uint_as_float(h[q] & 0xffff0000u);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f[q] = fminf(fmaxf((f[q] * pre) * inv, -E4M3_MAX), E4M3_MAX);      // clamp BEFORE the convert: beyond 448 it gives NaN
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+    return (unsigned)w;
+}
+
+// adaln_kernel<MAXV> (LayerNorm form) up to the modulated row, then the quantiser. A thread's vector vi covers columns 4 vi .. 4 vi + 3 < C:
+// bytes [4 vi, 4 vi + 4) of q row t (ldq >= C), one dword store.
+template <int MAXV>
+__global__ __launch_bounds__(NT) void adaln_e4m3_kernel(const float* __restrict__ x, int64_t ldx, int C, float eps,
+                                                        const float* __restrict__ mul, const float* __restrict__ add,
+                                                        int64_t tab_stride, const int32_t* __restrict__ row_idx,
+                                                        float add_one, unsigned char* __restrict__ qo, int64_t ldq,
+                                                        float* __restrict__ scale) {
+    __shared__ float red[8];
+    const int64_t t = blockIdx.x;
+    const float* xr = x + t * ldx;
+    const int nvec = C >> 2;
+    f32x4 v[MAXV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = threadIdx.x + i * NT;
+        if (vi < nvec) {
+            v[i] = *reinterpret_cast<const f32x4*>(xr + 4 * vi);
+            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        } else {
+            v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    constexpr bool HOIST = MAXV <= 3;
+    const int64_t row = row_idx ? (int64_t)row_idx[t] : 0;
+    const float* mr = mul + row * tab_stride;
+    const float* ar = add + row * tab_stride;
+    f32x4 m4v[MAXV], a4v[MAXV];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = threadIdx.x + i * NT;
+        if (HOIST && vi < nvec) {
+            m4v[i] = *reinterpret_cast<const f32x4*>(mr + 4 * vi);
+            a4v[i] = *reinterpret_cast<const f32x4*>(ar + 4 * vi);
+        }
+    }
+    const float mean = block_sum(s, red) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = threadIdx.x + i * NT;
+        if (vi < nvec) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = v[i][j] - mean;
+                q += d * d;
+            }
+        }
+    }
+    const float var = block_sum(q, red) / (float)C;
+    const float rstd = rsqrtf(var + eps);
+    u32x2 hb[MAXV];
+    float am = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = threadIdx.x + i * NT;
+        hb[i] = u32x2{0u, 0u};
+        if (vi < nvec) {
+            const f32x4 m4 = HOIST ? m4v[i] : *reinterpret_cast<const f32x4*>(mr + 4 * vi);
+            const f32x4 a4 = HOIST ? a4v[i] : *reinterpret_cast<const f32x4*>(ar + 4 * vi);
+            f32x4 y;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * (m4[j] + add_one) + a4[j];
+            hb[i][0] = pack_bf16x2(y[0], y[1]);
+            hb[i][1] = pack_bf16x2(y[2], y[3]);
+            am = absmax4(hb[i], am);
+        }
+    }
+    am = block_max(am, red);
+    const float sc = am > 0.f ? am / E4M3_MAX : 1.0f;
+    const float pre = sc < 0x1p-60f ? 0x1p64f : 1.0f;
+    const float inv = 1.0f / (sc * pre);
+    if (threadIdx.x == 0) scale[t] = sc;
+    unsigned char* qr = qo + t * ldq;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = threadIdx.x + i * NT;
+        if (vi < nvec) *reinterpret_cast<unsigned*>(qr + 4 * vi) = quant4(hb[i], pre, inv);
+    }
+}
+
+// adaln2_kernel's two rows per workgroup, then the quantiser on both: per row the arithmetic of adaln_e4m3_kernel<3> in the same order
+__global__ __launch_bounds__(NT) void adaln2_e4m3_kernel(const float* __restrict__ x, int64_t ldx, int T, int C, float eps,
+                                                         const float* __restrict__ mul, const float* __restrict__ add,
+                                                         int64_t tab_stride, const int32_t* __restrict__ row_idx,
+                                                         float add_one, unsigned char* __restrict__ qo, int64_t ldq,
+                                                         float* __restrict__ scale) {
+    constexpr int MAXV = 3;
+    __shared__ float red[16];
+    const int64_t t0 = 2 * (int64_t)blockIdx.x;
+    const bool two = t0 + 1 < T;                                   // (uniform) the last block of an odd T holds one row
+    const int64_t tr[2] = {t0, two ? t0 + 1 : t0};
+    const int nvec = C >> 2;
+    f32x4 v[2][MAXV], m4v[2][MAXV], a4v[2][MAXV];
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int vi = threadIdx.x + i * NT;
+            if (vi < nvec) {
+                v[r][i] = *reinterpret_cast<const f32x4*>(x + tr[r] * ldx + 4 * vi);
+            } else {
+                v[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    const int64_t mrow[2] = {row_idx ? (int64_t)row_idx[tr[0]] : 0, row_idx ? (int64_t)row_idx[tr[1]] : 0};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (r == 1 && mrow[1] == mrow[0]) {
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i) {
+                m4v[1][i] = m4v[0][i];
+                a4v[1][i] = a4v[0][i];
+            }
+            break;
+        }
+        const float* mr = mul + mrow[r] * tab_stride;
+        const float* ar = add + mrow[r] * tab_stride;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int vi = threadIdx.x + i * NT;
+            if (vi < nvec) {
+                m4v[r][i] = *reinterpret_cast<const f32x4*>(mr + 4 * vi);
+                a4v[r][i] = *reinterpret_cast<const f32x4*>(ar + 4 * vi);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) s[r] += (v[r][i][0] + v[r][i][1]) + (v[r][i][2] + v[r][i][3]);
+    block_sum2(s[0], s[1], red);
+    const float mean[2] = {s[0] / (float)C, s[1] / (float)C};
+    float q[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int vi = threadIdx.x + i * NT;
+            if (vi < nvec) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float d = v[r][i][j] - mean[r];
+                    q[r] += d * d;
+                }
+            }
+        }
+    block_sum2(q[0], q[1], red);
+    u32x2 hb[2][MAXV];
+    float am[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const float rstd = rsqrtf(q[r] / (float)C + eps);
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int vi = threadIdx.x + i * NT;
+            hb[r][i] = u32x2{0u, 0u};
+            if (vi < nvec) {
+                f32x4 y;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = (v[r][i][j] - mean[r]) * rstd * (m4v[r][i][j] + add_one) + a4v[r][i][j];
+                hb[r][i][0] = pack_bf16x2(y[0], y[1]);
+                hb[r][i][1] = pack_bf16x2(y[2], y[3]);
+                am[r] = absmax4(hb[r][i], am[r]);
+            }
+        }
+    }
+    block_max2(am[0], am[1], red);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (r == 1 && !two) break;
+        const float sc = am[r] > 0.f ? am[r] / E4M3_MAX : 1.0f;
+        const float pre = sc < 0x1p-60f ? 0x1p64f : 1.0f;
+        const float inv = 1.0f / (sc * pre);
+        if (threadIdx.x == 0) scale[tr[r]] = sc;
+        unsigned char* qr = qo + tr[r] * ldq;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int vi = threadIdx.x + i * NT;
+            if (vi < nvec) *reinterpret_cast<unsigned*>(qr + 4 * vi) = quant4(hb[r][i], pre, inv);
+        }
+    }
+}
+
 // RMSNorm(+RoPE) in place. Each thread owns NV 16-byte vectors (8 bf16) of the row:
 // vector index vi = tid + i*NT, i < NV; part(vi) = vi / (C/8) is wave-uniform since (C/8)%64==0.
 template <int NV>
@@ -434,6 +677,39 @@ extern "C" int yume_adaln_modulate(const float* x, int64_t ldx, int64_t T, int64
     else
         hipLaunchKernelGGL(adaln_kernel<8>, grid, block, 0, st, x, ldx, (int)C, eps, mul, add, tab_stride, row_idx, one, out, ldo, out_kind);
     YUME_CHECK_LAUNCH("adaln_modulate");
+    return YUME_OK;
+}
+
+extern "C" int yume_adaln_modulate_e4m3(const float* x, int64_t ldx, int64_t T, int64_t C, float eps, const float* mul,
+                                        const float* add, int64_t tab_stride, const int32_t* row_idx, int add_one,
+                                        void* q, int64_t ldq, float* scale, void* stream) {
+    YUME_REQUIRE(T >= 0 && C > 0 && C <= 8192, "adaln_modulate_e4m3: bad shape T=%lld C=%lld (C <= 8192)", (long long)T, (long long)C);
+    YUME_REQUIRE((C % 16) == 0, "adaln_modulate_e4m3: C=%lld must be a multiple of 16", (long long)C);
+    YUME_REQUIRE((ldq % 16) == 0 && ldq >= C, "adaln_modulate_e4m3: ldq=%lld must be a multiple of 16 and >= C", (long long)ldq);
+    YUME_REQUIRE((ldx % 4) == 0 && (tab_stride % 4) == 0, "adaln_modulate_e4m3: strides must be multiples of 4");
+    if (T == 0) return YUME_OK;
+    YUME_REQUIRE(x && mul && add && q && scale, "adaln_modulate_e4m3: NULL pointer");
+    YUME_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)scale % 4) == 0, "adaln_modulate_e4m3: q must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const float one = add_one ? 1.f : 0.f;
+    dim3 grid((unsigned)T), block(NT);
+    // the instance choice of yume_adaln_modulate at out_kind = 0, the same environment switch included
+    static const bool two_rows = [] { const char* v = getenv("YUME_NORM_TWO_ROWS"); return !v || atoi(v) != 0; }();
+    const bool use2 = two_rows && C <= NT * 4 * 3 && T >= 1024 && T < (1ll << 31);
+    if (norm_log())
+        norm_log_line(use2 ? "adaln2_e4m3" : "adaln_e4m3", use2 ? 0 : C <= NT * 4 * 3 ? 3 : C <= NT * 4 * 5 ? 5 : 8, T, C, 1, 0, ldx, ldq, tab_stride, 1, false,
+                      row_idx != nullptr);
+    unsigned char* qo = (unsigned char*)q;
+    if (use2)
+        hipLaunchKernelGGL(adaln2_e4m3_kernel, dim3((unsigned)((T + 1) / 2)), block, 0, st, x, ldx, (int)T, (int)C, eps, mul, add, tab_stride, row_idx, one,
+                           qo, ldq, scale);
+    else if (C <= NT * 4 * 3)
+        hipLaunchKernelGGL(adaln_e4m3_kernel<3>, grid, block, 0, st, x, ldx, (int)C, eps, mul, add, tab_stride, row_idx, one, qo, ldq, scale);
+    else if (C <= NT * 4 * 5)
+        hipLaunchKernelGGL(adaln_e4m3_kernel<5>, grid, block, 0, st, x, ldx, (int)C, eps, mul, add, tab_stride, row_idx, one, qo, ldq, scale);
+    else
+        hipLaunchKernelGGL(adaln_e4m3_kernel<8>, grid, block, 0, st, x, ldx, (int)C, eps, mul, add, tab_stride, row_idx, one, qo, ldq, scale);
+    YUME_CHECK_LAUNCH("adaln_modulate_e4m3");
     return YUME_OK;
 }
 

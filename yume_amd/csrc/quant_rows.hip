@@ -85,6 +85,9 @@ extern "C" int yume_quant_rows_e4m3(const void* x, int64_t ldx, int64_t R, int64
     if (R == 0) return YUME_OK;
     YUME_REQUIRE(x && q && scale, "quant_rows_e4m3: NULL pointer");
     YUME_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)scale % 4) == 0, "quant_rows_e4m3: x and q must be 16-byte aligned");
+    // YUME_NORM_LOG=1 (read once per process): one stderr line per launch, so a log can show that a path makes NO quantiser pass
+    static const bool log_on = [] { const char* v = getenv("YUME_NORM_LOG"); return v && atoi(v) != 0; }();
+    if (log_on) fprintf(stderr, "[quant] rows_e4m3 R=%lld K=%lld ldx=%lld ldq=%lld\n", (long long)R, (long long)K, (long long)ldx, (long long)ldq);
     hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)x, ldx, R, (int)K, (unsigned char*)q, ldq, scale);
     YUME_CHECK_LAUNCH("quant_rows_e4m3");

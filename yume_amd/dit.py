@@ -88,6 +88,10 @@ class DiTEngine:
         # QKV, o and the cross projections stay bf16. Off by default = the bf16 calls, bit for bit; env YUME_FP8_FFN=1 turns it on. Part of
         # the pack key: flipping it re-packs.
         self.fp8_ffn = os.environ.get("YUME_FP8_FFN", "0") == "1"
+        # r16: with fp8_ffn on (and only then), drop both quantiser passes: adaln_modulate_e4m3 -> gemm_f8 (MX_GELU) -> gemm_f8_mx (RESID), the
+        # activations between the two GEMMs as e4m3 with power-of-two scales per 32 columns (_ffn_block). Off by default = fp8_ffn as r15
+        # shipped it, bit for bit; env YUME_FP8_FFN_FUSED=1 turns it on. Not part of the pack key: the packed weights are the same.
+        self.fp8_ffn_fused = os.environ.get("YUME_FP8_FFN_FUSED", "0") == "1"
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -401,10 +405,29 @@ class DiTEngine:
                   variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
-            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, row_idx, True, h, 0, eps)
-            self._ffn(d, h, ff, xs, gate_ff, ts, row_idx)
+            self._ffn_block(d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, row_idx, eps)
             if cache is not None and cache[0] == "record" and i in cache[1]:
                 cache[2].append((xs - x_in).to(torch.bfloat16).unsqueeze(0))     # reference keeps [B, L, C] bf16
+
+    def _ffn_block(self, d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, row_idx, eps):
+        """the FFN adaLN and the FFN of a block, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike. With fp8_ffn_fused (where
+        fp8_ffn is on and the block qualified at pack time, and ffn_dim % 32 == 0) neither quantiser pass exists: the adaLN kernel emits the
+        e4m3 rows and their scales itself (bit-equal to adaln + quant_rows), ffn.0's GELU epilogue emits e4m3 with one E8M0 scale byte per row
+        and 32 columns (OCP MX; no bf16 ff is written), and ffn.2 consumes those scales inside the MFMA. Everything is row-local; the byte and
+        scale buffers are workspaces, allocated by the first eager forward."""
+        T = self._timed
+        if not (self.fp8_ffn_fused and "w1q" in d and ff.shape[1] % 32 == 0):
+            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, row_idx, True, h, 0, eps)
+            self._ffn(d, h, ff, xs, gate_ff, ts, row_idx)
+            return
+        n, F = h.shape[0], ff.shape[1]
+        hq = self._buf("ffn_hq", (n, h.shape[1]), torch.uint8, grow_rows=True)
+        sh = self._buf("ffn_sh", (n,), torch.float32, grow_rows=True)
+        fq = self._buf("ffn_fq", (n, F), torch.uint8, grow_rows=True)
+        fe = self._buf("ffn_fe", (n, (F // 32 + 15) // 16 * 16), torch.uint8, grow_rows=True)[:, :F // 32]     # (a pitch of whole 16-byte groups)
+        T("adaln", ops.adaln_modulate_e4m3, xs, scale_ff, shift_ff, ts, row_idx, True, hq, sh, eps)
+        T("gemm_ffn0", ops.gemm_f8_mxout, hq, sh, d["w1q"], d["s1"], d["b1"], fq, fe)
+        T("gemm_ffn2", ops.gemm_f8_mx, fq, fe, d["w2q"], d["s2"], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=row_idx)
 
     def _ffn(self, d, h, ff, xs, gate_ff, ts, row_idx):
         """the block's FFN on h bf16 [n, C]: ff = gelu(h W1^T + b1), xs += (ff W2^T + b2) * gate. With fp8_ffn (and a block that qualified at
@@ -456,8 +479,7 @@ class DiTEngine:
             T("attn_cross", ops.attn_fwd, qo, kc_i[:, i * C:(i + 1) * C], vct_i[i * C:(i + 1) * C], ao, n, n_img, H, accumulate=True,
               variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
         T("gemm_cross_o", ops.gemm_bf16, ao, d["wo_c"], d["bo_c"], xo, EPI_RESID, variant=self.gemm_variant)
-        T("adaln", ops.adaln_modulate, xo, scale_ff, shift_ff, ts, ro, True, ho, 0, eps)
-        self._ffn(d, ho, fo, xo, gate_ff, ts, ro)
+        self._ffn_block(d, xo, ho, fo, scale_ff, shift_ff, gate_ff, ts, ro, eps)
 
     # ------------------------------------------------------------------ one block through the engine (operator seam)
     @torch.no_grad()
@@ -760,8 +782,7 @@ class DiTEngine:
                   variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
-            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx2, True, h, 0, eps)
-            self._ffn(d, h, ff, xs, gate_ff, ts, ridx2)
+            self._ffn_block(d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, ridx2, eps)
 
     # ------------------------------------------------------------------ several samples in one pass
     @torch.no_grad()
@@ -929,8 +950,7 @@ class DiTEngine:
                   att, L, pitch, [n_img] * B, H, accumulate=True, variant=seg_variant, q_prescaled=self.q_prescale, kv_padded=True)
             T("gemm_cross_o", ops.gemm_bf16, att, d["wo_c"], d["bo_c"], xs, EPI_RESID, variant=self.gemm_variant)
             # --- FFN
-            T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, ridx, True, h, 0, eps)
-            self._ffn(d, h, ff, xs, gate_ff, ts, ridx)
+            self._ffn_block(d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, ridx, eps)
 
     def _forward_sp(self, xs, L, n_hist, tab, row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_last_weight=1.0):
         """Blocks + head on this rank's token chunk (sequence_parallel.py:121-152: chunk after the embeddings, gather

@@ -83,6 +83,23 @@ def adaln_modulate(x, mul, add, tab_stride, row_idx, add_one, out, out_kind=0, e
     return out
 
 
+def adaln_modulate_e4m3(x, mul, add, tab_stride, row_idx, add_one, q, scale, eps=1e-6):
+    """q u8 [T, C], scale fp32 [T] = quant_rows_e4m3(adaln_modulate(x, ..., out bf16)) in one kernel, bit for bit (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(x, "x", torch.float32)
+    _dev(q, "q", torch.uint8)
+    _dev(scale, "scale", torch.float32)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    T, C = x.shape
+    if tuple(q.shape) != (T, C) or scale.dim() != 1 or scale.numel() != T or not scale.is_contiguous():
+        raise RuntimeError(f"yume_amd.adaln_modulate_e4m3: x {tuple(x.shape)}, q {tuple(q.shape)}, scale {tuple(scale.shape)} do not fit")
+    rc = lib.yume_adaln_modulate_e4m3(xp, ldx, T, C, eps, mul.data_ptr(), add.data_ptr(), tab_stride, _ptr(row_idx),
+                                      1 if add_one else 0, qp, ldq, scale.data_ptr(), _stream())
+    _lib.check(rc, "yume_adaln_modulate_e4m3")
+    return q, scale
+
+
 def rmsnorm_f32(x, w, out, eps=1e-6):
     """out bf16 [T, C] = x * rsqrt(mean(x^2) + eps) * w (T5LayerNorm: no mean subtraction, no shift); x fp32 [T, C], w fp32 [C]."""
     lib = _lib.load()
@@ -198,6 +215,60 @@ def gemm_f8(aq, sa, wq, sw, bias, out, epi=EPI_BF16, gate=None, gate_stride=0, r
     rc = lib.yume_gemm_f8(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, epi, op, ldo, _ptr(gate), gate_stride,
                           _ptr(row_idx), _stream())
     _lib.check(rc, "yume_gemm_f8")
+    return out
+
+
+EPI_MX_GELU = 7
+
+
+def gemm_f8_mxout(aq, sa, wq, sw, bias, out, eo, epi=EPI_MX_GELU):
+    """the MX producer: out u8 [M, N] = e4m3(gelu_tanh(aq @ wq.T * sa[m] * sw[n] + bias) * 2^-e), eo u8 [M, N / 32] = e + 127 per row and
+    32 columns, e the smallest exponent with the block's amax <= 448 * 2^e (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(aq, "aq", torch.uint8)
+    _dev(wq, "wq", torch.uint8)
+    _dev(sa, "sa", torch.float32)
+    _dev(sw, "sw", torch.float32)
+    _dev(out, "out", torch.uint8)
+    _dev(eo, "eo", torch.uint8)
+    ap, lda = _rows(aq, "aq")
+    wp, ldw = _rows(wq, "wq")
+    M, K = aq.shape
+    N, K2 = wq.shape
+    if K != K2:
+        raise RuntimeError(f"yume_amd.gemm_f8_mxout: K mismatch {K} vs {K2}")
+    if sa.dim() != 1 or sa.numel() != M or not sa.is_contiguous() or sw.dim() != 1 or sw.numel() != N or not sw.is_contiguous():
+        raise RuntimeError(f"yume_amd.gemm_f8_mxout: scales sa {tuple(sa.shape)}, sw {tuple(sw.shape)} do not fit M={M}, N={N}")
+    op, ldo = _rows(out, "out")
+    ep, ldeo = _rows(eo, "eo")
+    if tuple(out.shape) != (M, N) or tuple(eo.shape) != (M, N // 32):
+        raise RuntimeError(f"yume_amd.gemm_f8_mxout: out {tuple(out.shape)}, eo {tuple(eo.shape)} do not fit M={M}, N={N}")
+    rc = lib.yume_gemm_f8_mxout(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, epi, op, ldo, ep, ldeo, _stream())
+    _lib.check(rc, "yume_gemm_f8_mxout")
+    return out, eo
+
+
+def gemm_f8_mx(aq, ea, wq, sw, bias, out, epi=EPI_F32, gate=None, gate_stride=0, row_idx=None):
+    """the MX consumer: acc = sum over 32-k blocks of 2^(ea[m, b] - 127) * (aq @ wq.T restricted to the block); y = acc * sw[n] + bias;
+    epilogue F32 or RESID. ea u8 [M, K / 32] with a row pitch that is a multiple of 16 bytes (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(aq, "aq", torch.uint8)
+    _dev(wq, "wq", torch.uint8)
+    _dev(ea, "ea", torch.uint8)
+    _dev(sw, "sw", torch.float32)
+    ap, lda = _rows(aq, "aq")
+    wp, ldw = _rows(wq, "wq")
+    ep, ldea = _rows(ea, "ea")
+    M, K = aq.shape
+    N, K2 = wq.shape
+    if K != K2:
+        raise RuntimeError(f"yume_amd.gemm_f8_mx: K mismatch {K} vs {K2}")
+    if tuple(ea.shape) != (M, K // 32) or sw.dim() != 1 or sw.numel() != N or not sw.is_contiguous():
+        raise RuntimeError(f"yume_amd.gemm_f8_mx: scales ea {tuple(ea.shape)}, sw {tuple(sw.shape)} do not fit M={M}, N={N}, K={K}")
+    op, ldo = _rows(out, "out")
+    rc = lib.yume_gemm_f8_mx(ap, lda, ep, ldea, wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, epi, op, ldo, _ptr(gate), gate_stride,
+                             _ptr(row_idx), _stream())
+    _lib.check(rc, "yume_gemm_f8_mx")
     return out
 
 
