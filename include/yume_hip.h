@@ -486,6 +486,16 @@ int yume_vae_pack_input(const void* x, int in_bf16, int64_t C, int64_t T, int64_
                         const float* mul, const float* add, void* out, int64_t Cpad, void* stream);
 int yume_vae_unpack_output(const void* x, int64_t ldx, int64_t T, int64_t H, int64_t W, int64_t Cv, int ps,
                            const float* sub, const float* mul, float lo, float hi, float* out, void* stream);
+/* env YUME_VAE_LOG=1 (read once per process, like YUME_NORM_LOG): every kernel launch of yume_vae_rmsnorm_silu, yume_vae_dupup_add,
+ * yume_vae_avgdown_add, yume_softmax_rows, yume_vae_pack_input and yume_vae_unpack_output prints one stderr line `[vae] <instance> k=v ...`:
+ *   rms<LPR,NV> | rms_g<G,NVL,RI> | rms_flat<NVEC,NVL,RI,silu,beta>   M= C= ldx= ldy= silu= beta=
+ *   dupup | dupup_lines<Q> | avgdown | avgdown_lines<RR>             Tin= Hin= Win= Cin= Cout= ft= fs= toff= ldx= ldy= lines= gx= gy=
+ *   softmax_rows | softmax_rows_reg<NV>                              R= n= lds= ldp=
+ *   pack<f32|bf16>                                                   C= T= H= W= ps= Cpad= affine= grid=
+ *   unpack                                                           T= H= W= Cv= ps= ldx= affine= clamp= grid=
+ * (avgdown has no toff: 0; the general shortcut kernels' grid is gx workgroups of a one-dimensional stride loop, gy = 1.) The routes:
+ * YUME_VAE_NORM_G / YUME_VAE_NORM_FLAT (read once per process), YUME_VAE_SHORTCUT_LINES / YUME_VAE_SOFTMAX_REG (read per call).
+ * tests/vae_op_cases.py holds one row per instance. */
 
 /* ---- post-decode frame conversion ---------------------------------------------------------------
  * replaces: fastvideo/sample/sample_5b.py:491-500 save_video -> diffusers==0.32.0 VideoProcessor.postprocess_video

@@ -617,6 +617,30 @@ inline unsigned grid_for(int64_t total, int per_block = 256, int64_t cap = 16384
     return (unsigned)nb;
 }
 
+// YUME_VAE_LOG=1: one stderr line per kernel launch of the six VAE entry points below, naming the kernel instance the call ran on and the
+// integers that decided it (read once per process)
+bool vae_log() {
+    static const bool on = [] { const char* v = getenv("YUME_VAE_LOG"); return v && atoi(v) != 0; }();
+    return on;
+}
+void vae_log_norm(const char* form, int a, int b, int c, int d, int e, int64_t M, int64_t C, int64_t ldx, int64_t ldy, int silu_on, bool beta) {
+    char name[48];
+    if (d >= 0) snprintf(name, sizeof(name), "%s<%d,%d,%d,%d,%d>", form, a, b, c, d, e);
+    else if (c >= 0) snprintf(name, sizeof(name), "%s<%d,%d,%d>", form, a, b, c);
+    else snprintf(name, sizeof(name), "%s<%d,%d>", form, a, b);
+    fprintf(stderr, "[vae] %s M=%lld C=%lld ldx=%lld ldy=%lld silu=%d beta=%d\n", name, (long long)M, (long long)C, (long long)ldx, (long long)ldy,
+            silu_on ? 1 : 0, beta ? 1 : 0);
+}
+void vae_log_shortcut(const char* form, int targ, int64_t Tin, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout, int ft, int fs, int toff,
+                      int64_t ldx, int64_t ldy, int64_t lines, unsigned gx, unsigned gy) {
+    char name[32];
+    if (targ > 0) snprintf(name, sizeof(name), "%s<%d>", form, targ);
+    else snprintf(name, sizeof(name), "%s", form);
+    fprintf(stderr, "[vae] %s Tin=%lld Hin=%lld Win=%lld Cin=%lld Cout=%lld ft=%d fs=%d toff=%d ldx=%lld ldy=%lld lines=%lld gx=%u gy=%u\n", name,
+            (long long)Tin, (long long)Hin, (long long)Win, (long long)Cin, (long long)Cout, ft, fs, toff, (long long)ldx, (long long)ldy,
+            (long long)lines, gx, gy);
+}
+
 }  // namespace
 
 extern "C" int yume_vae_rmsnorm_silu(const void* x, int64_t ldx, int64_t M, int64_t C, const float* gamma, const float* beta,
@@ -628,6 +652,7 @@ extern "C" int yume_vae_rmsnorm_silu(const void* x, int64_t ldx, int64_t M, int6
     unsigned short* yp = (unsigned short*)y;
     const int nvec = (int)(C / 8);
 #define LAUNCH_RMS(LPR, NV)                                                                                          \
+    if (vae_log()) vae_log_norm("rms", LPR, NV, -1, -1, -1, M, C, ldx, ldy, silu_on, beta != nullptr);                \
     hipLaunchKernelGGL((rmsnorm_silu_kernel<LPR, NV>), dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), \
                        dim3(256), 0, st, xp, ldx, M, (int)C, gamma, beta, silu_on, yp, ldy)
     // the every-lane-busy form where C / 8 = G * NVL with G a power of two <= 64 and NVL in {1, 3, 5} (YUME_VAE_NORM_G=0: the form above)
@@ -636,20 +661,22 @@ extern "C" int yume_vae_rmsnorm_silu(const void* x, int64_t ldx, int64_t M, int6
     while (G < 64 && (nvec % (2 * G)) == 0) G *= 2;
     const int nvl = nvec / G;
 #define LAUNCH_RMS_G(GG, NVL, RI)                                                                                                    \
+    if (vae_log()) vae_log_norm("rms_g", GG, NVL, RI, -1, -1, M, C, ldx, ldy, silu_on, beta != nullptr);                             \
     hipLaunchKernelGGL((rmsnorm_silu_g_kernel<GG, NVL, RI>), dim3((unsigned)((M + RI * 4 * (64 / GG) - 1) / (RI * 4 * (64 / GG)))), \
                        dim3(256), 0, st, xp, ldx, M, (int)C, gamma, beta, silu_on, yp, ldy)
 #define LAUNCH_RMS_GN(NVL, RI)                                                                              \
     switch (G) {                                                                                            \
-        case 1: LAUNCH_RMS_G(1, NVL, RI); break;   case 2: LAUNCH_RMS_G(2, NVL, RI); break;                \
-        case 4: LAUNCH_RMS_G(4, NVL, RI); break;   case 8: LAUNCH_RMS_G(8, NVL, RI); break;                \
-        case 16: LAUNCH_RMS_G(16, NVL, RI); break; case 32: LAUNCH_RMS_G(32, NVL, RI); break;              \
-        default: LAUNCH_RMS_G(64, NVL, RI); break;                                                          \
+        case 1: { LAUNCH_RMS_G(1, NVL, RI); } break;   case 2: { LAUNCH_RMS_G(2, NVL, RI); } break;        \
+        case 4: { LAUNCH_RMS_G(4, NVL, RI); } break;   case 8: { LAUNCH_RMS_G(8, NVL, RI); } break;        \
+        case 16: { LAUNCH_RMS_G(16, NVL, RI); } break; case 32: { LAUNCH_RMS_G(32, NVL, RI); } break;      \
+        default: { LAUNCH_RMS_G(64, NVL, RI); } break;                                                      \
     }
     // contiguous rows of 96 / 192 / 384 or 160 / 320 / 640 channels: the flat form (YUME_VAE_NORM_FLAT=0: the grouped one)
     static const bool flat = [] { const char* v = getenv("YUME_VAE_NORM_FLAT"); return !v || atoi(v) != 0; }();
 #define LAUNCH_RMS_F(NVEC, NVL, RI)                                                                                                         \
     do {                                                                                                                                    \
         const unsigned nb = (unsigned)((M * NVEC + (int64_t)4 * RI * NVL * 64 - 1) / ((int64_t)4 * RI * NVL * 64));                         \
+        if (vae_log()) vae_log_norm("rms_flat", NVEC, NVL, RI, silu_on ? 1 : 0, beta ? 1 : 0, M, C, ldx, ldy, silu_on, beta != nullptr);    \
         if (silu_on && !beta) hipLaunchKernelGGL((rmsnorm_silu_flat_kernel<NVEC, NVL, RI, true, false>), dim3(nb), dim3(256), 0, st, xp, M, gamma, beta, yp); \
         else if (silu_on) hipLaunchKernelGGL((rmsnorm_silu_flat_kernel<NVEC, NVL, RI, true, true>), dim3(nb), dim3(256), 0, st, xp, M, gamma, beta, yp);      \
         else if (!beta) hipLaunchKernelGGL((rmsnorm_silu_flat_kernel<NVEC, NVL, RI, false, false>), dim3(nb), dim3(256), 0, st, xp, M, gamma, beta, yp);      \
@@ -665,13 +692,13 @@ extern "C" int yume_vae_rmsnorm_silu(const void* x, int64_t ldx, int64_t M, int6
     else if (grouped && nvl == 1) { LAUNCH_RMS_GN(1, 4); }
     else if (grouped && nvl == 3) { LAUNCH_RMS_GN(3, 2); }
     else if (grouped && nvl == 5) { LAUNCH_RMS_GN(5, 1); }
-    else if (nvec <= 8) LAUNCH_RMS(8, 1);
-    else if (nvec <= 16) LAUNCH_RMS(16, 1);
-    else if (nvec <= 32) LAUNCH_RMS(32, 1);
-    else if (nvec <= 64) LAUNCH_RMS(64, 1);
-    else if (nvec <= 128) LAUNCH_RMS(64, 2);
-    else if (nvec <= 256) LAUNCH_RMS(64, 4);
-    else LAUNCH_RMS(64, 8);
+    else if (nvec <= 8) { LAUNCH_RMS(8, 1); }
+    else if (nvec <= 16) { LAUNCH_RMS(16, 1); }
+    else if (nvec <= 32) { LAUNCH_RMS(32, 1); }
+    else if (nvec <= 64) { LAUNCH_RMS(64, 1); }
+    else if (nvec <= 128) { LAUNCH_RMS(64, 2); }
+    else if (nvec <= 256) { LAUNCH_RMS(64, 4); }
+    else { LAUNCH_RMS(64, 8); }
 #undef LAUNCH_RMS_F
 #undef LAUNCH_RMS_GN
 #undef LAUNCH_RMS_G
@@ -701,14 +728,16 @@ extern "C" int yume_vae_dupup_add(const void* x, int64_t ldx, int64_t Tin, int64
             if ((cv & (cv - 1)) == 0) { cv_shift = 0; while ((1ll << cv_shift) < cv) ++cv_shift; }
             const unsigned gx = (unsigned)((Wo * cv + 1023) / 1024);      // four pixels-by-8-channels per thread
 #define LAUNCH_DUP(QQ)                                                                                                                          \
+    if (vae_log()) vae_log_shortcut("dupup_lines", QQ, Tin, Hin, Win, Cin, Cout, ft, fs, toff, ldx, ldy, lines, gx, (unsigned)lines);           \
     hipLaunchKernelGGL(dupup_add_lines_kernel<QQ>, dim3(gx, (unsigned)lines), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, \
                        (int)Hin, (int)Win, (unsigned short*)y, ldy, (int)Ho, (int)Wo, (int)cv, cv_shift, ft, fs, toff, rep_shift)
-            if (Q == 1) LAUNCH_DUP(1); else if (Q == 2) LAUNCH_DUP(2); else LAUNCH_DUP(4);
+            if (Q == 1) { LAUNCH_DUP(1); } else if (Q == 2) { LAUNCH_DUP(2); } else { LAUNCH_DUP(4); }
 #undef LAUNCH_DUP
             YUME_CHECK_LAUNCH("vae_dupup_add");
             return YUME_OK;
         }
     }
+    if (vae_log()) vae_log_shortcut("dupup", 0, Tin, Hin, Win, Cin, Cout, ft, fs, toff, ldx, ldy, To * Hin * fs, grid_for(total), 1u);
     hipLaunchKernelGGL(dupup_add_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
                        ldx, (int)Tin, (int)Hin, (int)Win, (int)Cin, (unsigned short*)y, ldy, (int)To, (int)Cout, ft, fs, toff);
     YUME_CHECK_LAUNCH("vae_dupup_add");
@@ -734,14 +763,17 @@ extern "C" int yume_vae_avgdown_add(const void* x, int64_t ldx, int64_t Tin, int
             if ((cv & (cv - 1)) == 0) { cv_shift = 0; while ((1ll << cv_shift) < cv) ++cv_shift; }
             const unsigned gx = (unsigned)((Wo * cv + 1023) / 1024);      // four pixels-by-8-channels per thread
 #define LAUNCH_AVG(R_)                                                                                                                            \
+    if (vae_log()) vae_log_shortcut("avgdown_lines", R_, Tin, Hin, Win, Cin, Cout, ft, fs, 0, ldx, ldy, lines, gx, (unsigned)lines);              \
     hipLaunchKernelGGL(avgdown_add_lines_kernel<R_>, dim3(gx, (unsigned)lines), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, \
                        (int)Hin, (int)Win, (unsigned short*)y, ldy, (int)Ho, (int)Wo, (int)cv, cv_shift, ft, fs, (int)G, (int)padt)
-            if (RR == 1) LAUNCH_AVG(1); else if (RR == 2) LAUNCH_AVG(2); else if (RR == 4) LAUNCH_AVG(4); else LAUNCH_AVG(8);
+            if (RR == 1) { LAUNCH_AVG(1); } else if (RR == 2) { LAUNCH_AVG(2); } else if (RR == 4) { LAUNCH_AVG(4); } else { LAUNCH_AVG(8); }
 #undef LAUNCH_AVG
             YUME_CHECK_LAUNCH("vae_avgdown_add");
             return YUME_OK;
         }
     }
+    if (vae_log())
+        vae_log_shortcut("avgdown", 0, Tin, Hin, Win, Cin, Cout, ft, fs, 0, ldx, ldy, ((Tin + padt) / ft) * (Hin / fs), grid_for(total), 1u);
     hipLaunchKernelGGL(avgdown_add_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
                        ldx, (int)Tin, (int)Hin, (int)Win, (int)Cin, (unsigned short*)y, ldy, (int)Cout, ft, fs);
     YUME_CHECK_LAUNCH("vae_avgdown_add");
@@ -756,13 +788,17 @@ extern "C" int yume_softmax_rows(const float* S, int64_t lds_, int64_t R, int64_
         const char* ev = getenv("YUME_VAE_SOFTMAX_REG");
         const bool reg_ok = (!ev || atoi(ev) != 0) && (lds_ % 4) == 0 && (ldp % 4) == 0 && ((uintptr_t)S % 16) == 0 && ((uintptr_t)P % 8) == 0 &&
                             lds_ >= (n + 3) / 4 * 4;
-#define LAUNCH_SM(NV) hipLaunchKernelGGL(softmax_rows_reg_kernel<NV>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, S, lds_, (int)n, scale, (unsigned short*)P, ldp)
-        if (reg_ok && n <= 1024 * 2) LAUNCH_SM(2);
-        else if (reg_ok && n <= 1024 * 4) LAUNCH_SM(4);
-        else if (reg_ok && n <= 1024 * 8) LAUNCH_SM(8);
-        else
+#define LAUNCH_SM(NV)                                                                                                                     \
+    if (vae_log()) fprintf(stderr, "[vae] softmax_rows_reg<%d> R=%lld n=%lld lds=%lld ldp=%lld\n", NV, (long long)R, (long long)n, (long long)lds_, (long long)ldp); \
+    hipLaunchKernelGGL(softmax_rows_reg_kernel<NV>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, S, lds_, (int)n, scale, (unsigned short*)P, ldp)
+        if (reg_ok && n <= 1024 * 2) { LAUNCH_SM(2); }
+        else if (reg_ok && n <= 1024 * 4) { LAUNCH_SM(4); }
+        else if (reg_ok && n <= 1024 * 8) { LAUNCH_SM(8); }
+        else {
+            if (vae_log()) fprintf(stderr, "[vae] softmax_rows R=%lld n=%lld lds=%lld ldp=%lld\n", (long long)R, (long long)n, (long long)lds_, (long long)ldp);
             hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, S, lds_, (int)n, scale,
                                (unsigned short*)P, ldp);
+        }
 #undef LAUNCH_SM
     }
     YUME_CHECK_LAUNCH("softmax_rows");
@@ -776,6 +812,9 @@ extern "C" int yume_vae_pack_input(const void* x, int in_bf16, int64_t C, int64_
     YUME_REQUIRE((mul == nullptr) == (add == nullptr), "vae_pack_input: mul and add go together");
     const int64_t total = T * (H / ps) * (W / ps) * Cpad;
     hipStream_t st = (hipStream_t)stream;
+    if (vae_log())
+        fprintf(stderr, "[vae] pack<%s> C=%lld T=%lld H=%lld W=%lld ps=%d Cpad=%lld affine=%d grid=%u\n", in_bf16 ? "bf16" : "f32", (long long)C, (long long)T,
+                (long long)H, (long long)W, ps, (long long)Cpad, mul ? 1 : 0, grid_for(total));
     if (in_bf16)
         hipLaunchKernelGGL(pack_input_kernel<true>, dim3(grid_for(total)), dim3(256), 0, st, x, (int)C, (int)T, (int)H, (int)W, ps, mul, add, (unsigned short*)out, (int)Cpad);
     else
@@ -790,6 +829,9 @@ extern "C" int yume_vae_unpack_output(const void* x, int64_t ldx, int64_t T, int
     YUME_REQUIRE(ps >= 1 && (Cv % (ps * ps)) == 0 && ldx >= Cv, "vae_unpack_output: bad shape");
     YUME_REQUIRE((mul == nullptr) == (sub == nullptr), "vae_unpack_output: sub and mul go together");
     const int64_t total = (Cv / (ps * ps)) * T * H * ps * W * ps;
+    if (vae_log())
+        fprintf(stderr, "[vae] unpack T=%lld H=%lld W=%lld Cv=%lld ps=%d ldx=%lld affine=%d clamp=%d grid=%u\n", (long long)T, (long long)H, (long long)W,
+                (long long)Cv, ps, (long long)ldx, mul ? 1 : 0, lo < hi ? 1 : 0, grid_for(total));
     hipLaunchKernelGGL(unpack_output_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
                        ldx, (int)T, (int)H, (int)W, (int)Cv, ps, sub, mul, lo, hi, out);
     YUME_CHECK_LAUNCH("vae_unpack_output");
