@@ -168,6 +168,16 @@ int yume_quant_rows_e4m3(const void* x, int64_t ldx, int64_t R, int64_t K, void*
 int yume_gemm_f8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
                  const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
                  const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
+/* yume_gemm_f8_splitt (the QKV form): yume_gemm_f8's operands, sum and scales, y = acc * sa[m] * sw[n] + bias[n], stored as
+ * YUME_EPI_BF16_SPLITT of yume_gemm_bf16 stores it: columns n < n_split to out[m, n] (bf16, row-major, row stride ldo elements),
+ * columns n >= n_split to outT[n - n_split, m] (bf16, K-major, row stride ldt elements). V^T columns m >= M and rows >= N - n_split
+ * are NOT written, out is never written at columns >= n_split. (yume_gemm_f8 itself keeps answering YUME_EUNSUP to that epilogue.)
+ * Checks (YUME_EINVAL): those of yume_gemm_f8 on the operands, and 0 <= n_split <= N, n_split % 256 == 0 (a 256 x 256 tile lies
+ * wholly on one side); n_split > 0: out non-NULL, 16-byte aligned, ldo % 4 == 0, ldo >= n_split; n_split < N: outT non-NULL,
+ * 16-byte aligned, ldt % 8 == 0, ldt >= M. */
+int yume_gemm_f8_splitt(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
+                        const float* bias, int64_t M, int64_t N, int64_t K,
+                        void* out, int64_t ldo, void* outT, int64_t ldt, int64_t n_split, void* stream);
 
 /* ---- FP8 FFN without quantiser passes (r16; functions added, no argument list changed: ABI 9) ------------------------------
  * yume_adaln_modulate_e4m3: yume_adaln_modulate(..., out_kind = 0) followed by yume_quant_rows_e4m3 on its bf16 output, in one

@@ -28,6 +28,7 @@ SIGNATURES = {
     "yume_gemm_bf16_ws": [_P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P, _L, _L, _I, _P, _L, _P],
     "yume_quant_rows_e4m3": [_P, _L, _L, _L, _P, _L, _P, _P],
     "yume_gemm_f8": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P],
+    "yume_gemm_f8_splitt": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _L, _L, _P],
     "yume_gemm_f8_mxout": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P],
     "yume_gemm_f8_mx": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P],
     "yume_rmsnorm_f32": [_P, _L, _L, _L, _F, _P, _P, _L, _P],

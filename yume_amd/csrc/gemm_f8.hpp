@@ -1,5 +1,6 @@
 // gemm_f8.hpp — the e4m3 x e4m3 GEMM of the fp8 FFN option (r15):   acc[m,n] = sum_k Aq[m,k] * Wq[n,k]  (fp32),
-//   y = acc * sa[m] * sw[n] + bias[n],  then the epilogue (BF16 / GELU tanh / F32 / RESID, as gemm_core.hpp defines them).
+//   y = acc * sa[m] * sw[n] + bias[n],  then the epilogue (BF16 / GELU tanh / F32 / RESID, as gemm_core.hpp defines them; r18: SPLITT,
+//   q | k row-major and V as the K-major V^T image, through yume_gemm_f8_splitt — f8_epilogue_vt below).
 //
 // Structure: gemm_w4.hpp's tile and wave layout, gemm128_kernel's (gemm_core.hpp) loop.
 //   * ONE 256 x 256 output tile per workgroup, 4 waves (2 x 2), wave (wr, wc) owns rows wr*128 + [0,128), columns wc*128 + [0,128): 8 x 8
@@ -73,6 +74,52 @@ __device__ __forceinline__ i32x8 f8_frag(const char* oper, int row, int lane) {
     return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
+// ---- (r18) the transposed side of YUME_EPI_BF16_SPLITT: columns n >= n_split leave as the K-major V^T image outT[n - n_split][m].
+// The accumulators keep the SWAP orientation (a lane holds C[m][n .. n + 3]), so the tile's bf16 image is written TRANSPOSED into the LDS
+// the operand buffers free — image rows = features n, image columns = tokens m, gemm_w4.hpp's layout ([256][512 B], 16-byte chunk c of row
+// r at chunk c ^ (r & 31)) — and leaves through w4_store_image with rows and columns exchanged, as w4_epilogue<SPLITT, !SWAP> does.
+// A lane's four values belong to four image rows at one 2-byte column. Lanes l15 and l15 ^ 1 (tokens m, m + 1) exchange one packed pair
+// (DPP quad_perm [1, 0, 3, 2]): the even lane then holds (m, m + 1) of columns n, n + 1, the odd lane of columns n + 2, n + 3 — two dword
+// writes per lane and tile in place of four 2-byte ones. Banks (ds_write_b32: dword address % 32, conflicts inside a 32-lane half = both values of l4 & 1, all l15): a
+// lane's dword is ((l15 >> 1) & 3) of chunk (16 wr + 2 i + (l15 >> 3)) ^ (r & 31) with r & 7 = 4 (l4 & 1) + 2 (l15 & 1) + s: chunk bit 0 =
+// l15 >> 3, bit 1 = l15 & 1, bit 2 = l4 & 1 (XORed with constants of the tile) — 32 lanes, 32 different banks, no conflict.
+//   image byte of (tile i, j, s = 0 / 1, lane) = r * 512 + ((chunk ^ (r & 31)) << 4) + 4 ((l15 >> 1) & 3),  r = 128 wc + 16 j + 4 l4 + 2 (l15 & 1) + s
+//     = vbase + (16 j + s) * 512 + ((wr ^ (j & 1)) << 8) + (lx ^ ((2 i | s) << 4)):  r < 256, chunk < 32 — inside the 128 KiB image.
+// Rows m >= M (computed from the clamped row M - 1) and columns n >= N sit in the image and are not stored: w4_store_image takes
+// rows_valid = min(256, N - n0) and cols_valid = min(256, M - m0), its last partial chunk element by element.
+template <class Col>
+__device__ __forceinline__ void f8_epilogue_vt(const f32x4 (&acc)[8][8], const float (&sa)[8], Col col, const Problem& p, const Epilogue& e, int m0,
+                                               int n0, char* smem) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const bool odd = (l15 & 1) != 0;
+    const int x0 = 4 * l4 + 2 * (l15 & 1);
+    const unsigned vbase = (unsigned)((wc * 128 + x0) * 512 + ((l15 >> 1) & 3) * 4);
+    const unsigned lx = (unsigned)((x0 | (l15 >> 3)) << 4);
+    __syncthreads();                                                // every wave is done with the operand buffers: the image reuses them
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        f32x4 sw, b;
+        col(j, sw, b);
+        const unsigned jb = vbase + (unsigned)(16 * j * 512) + (unsigned)((wr ^ (j & 1)) << 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f32x4 v = (acc[i][j] * sa[i]) * sw + b;
+            const unsigned p01 = pack_bf16x2(v[0], v[1]), p23 = pack_bf16x2(v[2], v[3]);
+            const unsigned got = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? p01 : p23), 0xB1, 0xf, 0xf, false);   // from lane ^ 1
+            const unsigned keep = odd ? p23 : p01;
+            const unsigned lo = odd ? got : keep, hi = odd ? keep : got;        // token m (even) / m + 1 of this lane's two columns
+            *reinterpret_cast<unsigned*>(smem + jb + (lx ^ (unsigned)((2 * i) << 4))) = (lo & 0xffffu) | (hi << 16);
+            *reinterpret_cast<unsigned*>(smem + jb + 512u + (lx ^ (unsigned)((2 * i + 1) << 4))) = (lo >> 16) | (hi & 0xffff0000u);
+        }
+    }
+    __syncthreads();
+    // V^T rows n0 - n_split .. + min(256, N - n0) - 1 (< N - n_split), columns m0 .. m0 + min(256, M - m0) - 1 (< M <= ldt)
+    gemm_w4::w4_store_image(smem, e.outT + (int64_t)(n0 - e.n_split) * e.ldt, e.ldt, 0, min(256, p.N - n0), m0, min(256, p.M - m0));
+}
+
 // MX (gemm_f8_mx_kernel): the row scales were applied inside the instruction, there is no sa (the factor is the literal 1)
 template <int EPI, bool MX = false>
 __device__ __forceinline__ void f8_epilogue(const f32x4 (&acc)[8][8], const Problem& p, const F8Args& f, const Epilogue& e, int m0, int n0, char* smem) {
@@ -92,7 +139,15 @@ __device__ __forceinline__ void f8_epilogue(const f32x4 (&acc)[8][8], const Prob
         sw = n < p.N ? *reinterpret_cast<const f32x4*>(f.sw + n) : f32x4{1.f, 1.f, 1.f, 1.f};
         b = (e.bias && n < p.N) ? *reinterpret_cast<const f32x4*>(e.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
     };
-    constexpr bool BF16_OUT = EPI == YUME_EPI_BF16 || EPI == YUME_EPI_BF16_GELU;
+    if constexpr (EPI == YUME_EPI_BF16_SPLITT) {
+        if (n0 >= e.n_split) {                                      // (workgroup-uniform) n_split % 256 == 0: a tile lies wholly on one side
+            f8_epilogue_vt(acc, sa, col, p, e, m0, n0, smem);
+            return;
+        }
+    }
+    // a SPLITT tile on the row-major side is a BF16 tile: n0 + 256 <= n_split <= N, nothing of it reaches a column >= n_split
+    constexpr int EPI_RM = EPI == YUME_EPI_BF16_SPLITT ? YUME_EPI_BF16 : EPI;
+    constexpr bool BF16_OUT = EPI_RM == YUME_EPI_BF16 || EPI_RM == YUME_EPI_BF16_GELU;
     if (BF16_OUT && (e.ldo % 8) == 0) {                            // (workgroup-uniform)
         const gemm_w4::ImageOff io = gemm_w4::w4_image_offsets(wr, wc, l15, l4);
         __syncthreads();                                            // every wave is done with the operand buffers: the image reuses them
@@ -123,7 +178,7 @@ __device__ __forceinline__ void f8_epilogue(const f32x4 (&acc)[8][8], const Prob
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int m = m0 + wr * 128 + 16 * i + l15, n = n0 + wc * 128 + 16 * j + 4 * l4;
-            if (m < p.M && n < p.N) store_row4<EPI>((acc[i][j] * sa[i]) * sw + b, m, n, p, e0);      // out[m, n .. n + 3], n + 3 < N
+            if (m < p.M && n < p.N) store_row4<EPI_RM>((acc[i][j] * sa[i]) * sw + b, m, n, p, e0);      // out[m, n .. n + 3], n + 3 < N
         }
     }
 }
@@ -365,6 +420,7 @@ inline int launch_f8(int epi, Problem p, const F8Args& f, const Epilogue& e, hip
         case YUME_EPI_F32: hipLaunchKernelGGL(gemm_f8_kernel<YUME_EPI_F32>, grid, block, 0, st, p, f, e); break;
         case YUME_EPI_RESID: hipLaunchKernelGGL(gemm_f8_kernel<YUME_EPI_RESID>, grid, block, 0, st, p, f, e); break;
         case EPI_MX_GELU: hipLaunchKernelGGL(gemm_f8_kernel<EPI_MX_GELU>, grid, block, 0, st, p, f, e); break;
+        case YUME_EPI_BF16_SPLITT: hipLaunchKernelGGL(gemm_f8_kernel<YUME_EPI_BF16_SPLITT>, grid, block, 0, st, p, f, e); break;
         default: hipLaunchKernelGGL(gemm_f8_kernel<YUME_EPI_BF16>, grid, block, 0, st, p, f, e); break;
     }
     YUME_CHECK_LAUNCH("gemm_f8");

@@ -92,6 +92,11 @@ class DiTEngine:
         # activations between the two GEMMs as e4m3 with power-of-two scales per 32 columns (_ffn_block). Off by default = fp8_ffn as r15
         # shipped it, bit for bit; env YUME_FP8_FFN_FUSED=1 turns it on. Not part of the pack key: the packed weights are the same.
         self.fp8_ffn_fused = os.environ.get("YUME_FP8_FFN_FUSED", "0") == "1"
+        # r18: the self-attention QKV projection and the cross-attention q projection in e4m3. An adaLN launch feeds each of them, so there is
+        # no quantiser pass: adaln_modulate_e4m3 -> gemm_f8_splitt (q | k row-major, V as the K-major V^T image) and adaln_modulate_e4m3
+        # (norm3) -> gemm_f8 (_qkv_step, _cross_q_step). o and cross-o stay bf16 (their input is the attention output). Independent of the two
+        # FFN options. Off by default = the bf16 calls, bit for bit; env YUME_FP8_QKV=1 turns it on. Part of the pack key: flipping it re-packs.
+        self.fp8_qkv = os.environ.get("YUME_FP8_QKV", "0") == "1"
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -110,7 +115,7 @@ class DiTEngine:
     def _param_key(self):
         # walked once per forward: (storage address, in-place version, dtype) of every parameter — a load_state_dict, an
         # optimizer step or a .to(dtype) re-packs; cheap next to one forward (≈1 k tensors), and cached per forward call
-        return (self.q_prescale, bool(self.fp8_ffn)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
+        return (self.q_prescale, bool(self.fp8_ffn), bool(self.fp8_qkv)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
 
     def _pack(self):
         m = self.model
@@ -184,6 +189,17 @@ class DiTEngine:
                         ops.quant_rows_e4m3(d[wk], d[qk_], d[sk_])
                 elif os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
                     sys.stderr.write(f"[fp8_ffn] block {len(blocks)} keeps bf16 FFN linears: dim={C} ffn_dim={m.ffn_dim} are not both multiples of 128\n")
+            if self.fp8_qkv:
+                log = os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0")
+                if C % 128 == 0:       # (K % 128 == 0 and n_split = 2 C a multiple of 256: every DiT the attention kernels take, head_dim 128)
+                    for wk, qk_, sk_ in (("wqkv", "wqkvq", "sqkv"),) + ((("wq_c", "wq_cq", "sq_c"),) if "n3w" in d else ()):
+                        d[qk_] = torch.empty(d[wk].shape, dtype=torch.uint8, device=dev)
+                        d[sk_] = torch.empty(d[wk].shape[0], dtype=torch.float32, device=dev)
+                        ops.quant_rows_e4m3(d[wk], d[qk_], d[sk_])
+                    if "n3w" not in d and log and not blocks:
+                        sys.stderr.write("[fp8_qkv] the blocks have no norm3 weights: the cross-attention q projection stays bf16\n")
+                elif log and not blocks:
+                    sys.stderr.write(f"[fp8_qkv] the blocks keep bf16 QKV / cross-q linears: dim={C} is not a multiple of 128\n")
             blocks.append(d)
         P["blocks"] = blocks
         # cross-attention K / V projections of ALL blocks as one weight: the conditioning tokens are the same for every block,
@@ -372,8 +388,7 @@ class DiTEngine:
                                     (kc_i, vct_i, n_img) if n_img else None, txt_last_weight, txt_variant)
                 continue
             # --- self attention
-            T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, row_idx, True, h, 0, eps)
-            T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk, EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+            self._qkv_step(d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps)
             if n_rope == L:
                 T("rmsnorm_rope", ops.rmsnorm_rope, qk, C, 2, d["nqk"], self.qk_eps, rope)
             elif n_rope == 0:
@@ -392,11 +407,7 @@ class DiTEngine:
                 sa = self.sp.exchange_out(of)
             T("gemm_o", ops.gemm_bf16, sa, d["wo"], d["bo"], xs, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=row_idx, variant=self.gemm_variant)
             # --- cross attention
-            if "n3w" in d:
-                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
-            else:
-                ops.cast_bf16(xs, L, h)
-            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:, :C], EPI_BF16, variant=self.gemm_variant)
+            self._cross_q_step(d, xs, h, qk[:, :C], eps)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:, :C], C, 1, d["nq_c"], self.qk_eps)
             T("attn_cross", ops.attn_fwd, qk[:, :C], kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], att, L, ntxt, H, variant=txt_variant,
               q_prescaled=self.q_prescale, kv_padded=True, last_key_weight=txt_last_weight)
@@ -408,6 +419,39 @@ class DiTEngine:
             self._ffn_block(d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, row_idx, eps)
             if cache is not None and cache[0] == "record" and i in cache[1]:
                 cache[2].append((xs - x_in).to(torch.bfloat16).unsqueeze(0))     # reference keeps [B, L, C] bf16
+
+    def _qkv_step(self, d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps):
+        """the first adaLN of a block and its QKV projection, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike: q | k into
+        qk [n, 2C], V as the K-major image vt[:, :n]. With fp8_qkv (and a block packed for it) the adaLN kernel emits the e4m3 rows and their
+        scales itself and the e4m3 GEMM writes both outputs (yume_gemm_f8_splitt); h is then not written. Row-local: the callers' row ranges
+        are handed on as they are. The byte and scale buffers are workspaces, allocated by the first eager forward."""
+        T = self._timed
+        if "wqkvq" not in d:
+            T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, row_idx, True, h, 0, eps)
+            T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk, EPI_BF16_SPLITT, out_t=vt, n_split=2 * self.model.dim, variant=self.gemm_variant)
+            return
+        n, C = h.shape
+        hq = self._buf("qkv_hq", (n, C), torch.uint8, grow_rows=True)
+        sh = self._buf("qkv_sh", (n,), torch.float32, grow_rows=True)
+        T("adaln", ops.adaln_modulate_e4m3, xs, scale_sa, shift_sa, ts, row_idx, True, hq, sh, eps)
+        T("gemm_qkv", ops.gemm_f8_splitt, hq, sh, d["wqkvq"], d["sqkv"], d["bqkv"], qk, vt, 2 * C)
+
+    def _cross_q_step(self, d, xs, h, q, eps):
+        """norm3 (or, without its weights, the plain cast) of xs [n, C] and the cross-attention q projection into q [n, C], behind the same four
+        bodies. With fp8_qkv (and norm3 weights: an adaLN launch has to be there to emit the bytes) the pair runs in e4m3 as _qkv_step's."""
+        T = self._timed
+        n, C = h.shape
+        if "wq_cq" not in d:
+            if "n3w" in d:
+                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
+            else:
+                ops.cast_bf16(xs, n, h)
+            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], q, EPI_BF16, variant=self.gemm_variant)
+            return
+        hq = self._buf("qkv_hq", (n, C), torch.uint8, grow_rows=True)
+        sh = self._buf("qkv_sh", (n,), torch.float32, grow_rows=True)
+        T("adaln", ops.adaln_modulate_e4m3, xs, d["n3w"], d["n3b"], 0, None, False, hq, sh, eps)
+        T("gemm_cross_q", ops.gemm_f8, hq, sh, d["wq_cq"], d["sq_c"], d["bq_c"], q, EPI_BF16)
 
     def _ffn_block(self, d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, row_idx, eps):
         """the FFN adaLN and the FFN of a block, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike. With fp8_ffn_fused (where
@@ -461,16 +505,11 @@ class DiTEngine:
         xo, ho, ao, fo, qo = xs[s:], h[s:], att[s:], ff[s:], qk[s:, :C]
         ro = row_idx[s:] if row_idx is not None else None
         n = L - s
-        T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, row_idx, True, h, 0, eps)
-        T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk, EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+        self._qkv_step(d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps)
         T("rmsnorm_rope", ops.rmsnorm_rope, qk, C, 2, d["nqk"], self.qk_eps, rope)
         T("attn_self", ops.attn_fwd, qo, qk[:, C:], vt, ao, n, L, H, variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
         T("gemm_o", ops.gemm_bf16, ao, d["wo"], d["bo"], xo, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ro, variant=self.gemm_variant)
-        if "n3w" in d:
-            T("adaln", ops.adaln_modulate, xo, d["n3w"], d["n3b"], 0, None, False, ho, 0, eps)
-        else:
-            ops.cast_bf16(xo, n, ho)
-        T("gemm_cross_q", ops.gemm_bf16, ho, d["wq_c"], d["bq_c"], qo, EPI_BF16, variant=self.gemm_variant)
+        self._cross_q_step(d, xo, ho, qo, eps)
         T("rmsnorm_rope", ops.rmsnorm_rope, qo, C, 1, d["nq_c"], self.qk_eps)
         T("attn_cross", ops.attn_fwd, qo, kc_t[:, i * C:(i + 1) * C], vct_t[i * C:(i + 1) * C], ao, n, ntxt, H, variant=txt_variant,
           q_prescaled=self.q_prescale, kv_padded=True, last_key_weight=txt_last_weight)
@@ -756,8 +795,7 @@ class DiTEngine:
             shift_ff, scale_ff, gate_ff = tb[:, 3], tb[:, 4], tb[:, 5]
             # --- self attention: block 0 once, on the L rows both legs share; later blocks over the stacked rows, one attention launch per leg
             n, ri, ro = (L, row_idx, rope) if i == 0 else (M, ridx2, rope2)
-            T("adaln", ops.adaln_modulate, xs[:n], scale_sa, shift_sa, ts, ri, True, h[:n], 0, eps)
-            T("gemm_qkv", ops.gemm_bf16, h[:n], d["wqkv"], d["bqkv"], qk[:n], EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+            self._qkv_step(d, xs[:n], scale_sa, shift_sa, ts, ri, h[:n], qk[:n], vt, eps)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:n], C, 2, d["nqk"], self.qk_eps, ro)
             if i > 0 and self.pair_self_batched:
                 T("attn_self", ops.attn_fwd_batch, qk[:M, :C], qk[:, C:], vt, att, 2, L, pitch, L, pitch, H, variant=self.batch_attn_variant,
@@ -769,11 +807,7 @@ class DiTEngine:
             if i == 0:
                 xs[pitch:].copy_(xs[:L])                                # the legs part here
             # --- cross attention
-            if "n3w" in d:
-                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
-            else:
-                ops.cast_bf16(xs, M, h)
-            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:M, :C], EPI_BF16, variant=self.gemm_variant)
+            self._cross_q_step(d, xs, h, qk[:M, :C], eps)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M, :C], C, 1, d["nq_c"], self.qk_eps)
             T("attn_cross", ops.attn_fwd_seg, qk[:M, :C], [kc[:, i * C:(i + 1) * C] for kc, _ in kv_t], [v[i * C:(i + 1) * C] for _, v in kv_t],
               att, L, pitch, n_txt, H, variant=txt_variant, q_prescaled=self.q_prescale, kv_padded=True, last_key_weights=txt_w)
@@ -927,18 +961,13 @@ class DiTEngine:
             shift_sa, scale_sa, gate_sa = tb[:, 0], tb[:, 1], tb[:, 2]
             shift_ff, scale_ff, gate_ff = tb[:, 3], tb[:, 4], tb[:, 5]
             # --- self attention: one launch over the (sample, head) pairs
-            T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, ridx, True, h, 0, eps)
-            T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk[:M], EPI_BF16_SPLITT, out_t=vt, n_split=2 * C, variant=self.gemm_variant)
+            self._qkv_step(d, xs, scale_sa, shift_sa, ts, ridx, h, qk[:M], vt, eps)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M], C, 2, d["nqk"], self.qk_eps, rope)
             T("attn_self", ops.attn_fwd_batch, qk[:M, :C], qk[:, C:], vt, att, B, L, pitch, L, pitch, H, variant=self.batch_attn_variant,
               q_prescaled=self.q_prescale, kv_padded=True)
             T("gemm_o", ops.gemm_bf16, att, d["wo"], d["bo"], xs, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ridx, variant=self.gemm_variant)
             # --- cross attention
-            if "n3w" in d:
-                T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)
-            else:
-                ops.cast_bf16(xs, M, h)
-            T("gemm_cross_q", ops.gemm_bf16, h, d["wq_c"], d["bq_c"], qk[:M, :C], EPI_BF16, variant=self.gemm_variant)
+            self._cross_q_step(d, xs, h, qk[:M, :C], eps)
             T("rmsnorm_rope", ops.rmsnorm_rope, qk[:M, :C], C, 1, d["nq_c"], self.qk_eps)
             T("attn_cross", ops.attn_fwd_seg, qk[:M, :C], [kc[:, i * C:(i + 1) * C] for kc, _ in kv_t], [v[i * C:(i + 1) * C] for _, v in kv_t],
               att, L, pitch, n_txt, H, variant=seg_variant, q_prescaled=self.q_prescale, kv_padded=True, last_key_weights=txt_w)

@@ -218,6 +218,38 @@ def gemm_f8(aq, sa, wq, sw, bias, out, epi=EPI_BF16, gate=None, gate_stride=0, r
     return out
 
 
+def gemm_f8_splitt(aq, sa, wq, sw, bias, out, out_t, n_split):
+    """gemm_f8's sum and scales with the QKV epilogue: columns n < n_split bf16 row-major into out [M, >= n_split], columns n >= n_split as
+    the K-major V^T image out_t[n - n_split, m] (bf16 [>= N - n_split, ldt >= M]); n_split % 256 == 0 (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(aq, "aq", torch.uint8)
+    _dev(wq, "wq", torch.uint8)
+    _dev(sa, "sa", torch.float32)
+    _dev(sw, "sw", torch.float32)
+    ap, lda = _rows(aq, "aq")
+    wp, ldw = _rows(wq, "wq")
+    M, K = aq.shape
+    N, K2 = wq.shape
+    if K != K2:
+        raise RuntimeError(f"yume_amd.gemm_f8_splitt: K mismatch {K} vs {K2}")
+    if sa.dim() != 1 or sa.numel() != M or not sa.is_contiguous() or sw.dim() != 1 or sw.numel() != N or not sw.is_contiguous():
+        raise RuntimeError(f"yume_amd.gemm_f8_splitt: scales sa {tuple(sa.shape)}, sw {tuple(sw.shape)} do not fit M={M}, N={N}")
+    op, ldo, tp, ldt = None, 0, None, 0
+    if out is not None:
+        _dev(out, "out", torch.bfloat16)
+        op, ldo = _rows(out, "out")
+        if out.shape[0] < M or out.shape[1] < n_split:
+            raise RuntimeError(f"yume_amd.gemm_f8_splitt: out {tuple(out.shape)} does not hold [{M}, {n_split}]")
+    if out_t is not None:
+        _dev(out_t, "out_t", torch.bfloat16)
+        tp, ldt = _rows(out_t, "out_t")
+        if out_t.shape[0] < N - n_split:
+            raise RuntimeError(f"yume_amd.gemm_f8_splitt: out_t {tuple(out_t.shape)} does not hold {N - n_split} rows")
+    rc = lib.yume_gemm_f8_splitt(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, op, ldo, tp, ldt, n_split, _stream())
+    _lib.check(rc, "yume_gemm_f8_splitt")
+    return out, out_t
+
+
 EPI_MX_GELU = 7
 
 
