@@ -507,6 +507,39 @@ int yume_vae_unpack_output(const void* x, int64_t ldx, int64_t T, int64_t H, int
  * YUME_VAE_NORM_G / YUME_VAE_NORM_FLAT (read once per process), YUME_VAE_SHORTCUT_LINES / YUME_VAE_SOFTMAX_REG (read per call).
  * tests/vae_op_cases.py holds one row per instance. */
 
+/* ---- FP8 residual convolutions of the VAE (r19; functions added, no argument list changed: ABI 9) ----------------------------
+ * The input of every ResidualBlock convolution is the output of an RMS_norm + SiLU launch, so the norm emits OCP MX e4m3 itself (bytes
+ * + one E8M0 scale byte 2^(byte - 127) per position and 32 consecutive channels) and the convolution takes the scale bytes into the
+ * scale operand of v_mfma_scale_f32_16x16x128_f8f6f4: a per-position scale does not factor out of a convolution, a block scale need not.
+ *
+ * yume_vae_rmsnorm_silu_mx (the producer): yume_vae_rmsnorm_silu(x, ldx, M, C, gamma, beta, silu, y, ldy = C) followed by an MX quantiser of
+ *     the bf16 y, in one kernel and without y, bit for bit: per row and block of 32 channels amax = max |y|, e = the smallest integer with
+ *     amax <= 448 * 2^e (the rule of YUME_EPI_MX_GELU; 0 for an all-zero block), e_out[m, c / 32] = e + 127, q[m, c] = e4m3_rne(clamp(y * 2^-e, +-448)).
+ *     q u8 [M, C] (row stride ldq bytes), e_out u8 [M, C / 32] (row stride lde). The norm's kernel forms differ in their last bits
+ *     (summation order, SiLU form); this call takes the form the norm takes for (C, ldx, ldy = C) and the same route switches.
+ *     Checks (YUME_EINVAL): C % 32 == 0, C <= 4096, ldx % 8 == 0, ldx >= C, ldq % 8 == 0, ldq >= C, lde % 4 == 0, lde >= C / 32, x / q / gamma /
+ *     beta 16-byte aligned, e_out 4-byte aligned. Bytes beyond C of a q row, scale bytes beyond C / 32 and rows beyond M are not written.
+ *     YUME_VAE_LOG=1: one line `[vae] rms_mx <form> M= C= ldx= ldq= lde= silu= beta=`.
+ * yume_conv3d_cl_f8mx (the consumer):
+ *     out[(to,ho,wo), co] = bias[co] + sw[co] * sum_{dt,dh,dw} sum_b 2^(xe[pos+tap, b] - 127) * sum_{c in block b} xq[pos+tap, c] * Wq[co, tap*Cin + c]
+ *     with tap = (dt*kh + dh)*kw + dw and the cache frames and zero padding of yume_conv3d_cl; fp32 sums walked (dt, channel tile of 128, dh, dw).
+ *     xq u8 [Tin,Hin,Win,ldc], xe u8 [Tin,Hin,Win,lde]; cacheq / cachee: the last two input frames of the previous chunk in the same layouts,
+ *     both NULL or both given; Wq u8 [Cout, ldw] e4m3, sw fp32 [Cout] (the weight's per-output-channel scale), bias fp32 [Cout] or NULL;
+ *     zero_page >= 16 zero bytes. epi: YUME_EPI_BF16, YUME_EPI_F32, YUME_CONV_EPI_ADD (add bf16 [M, ldadd]).
+ *     Accepted: stride 1, ups = 0, kt / kh / kw in {1, 3} with pt = kt - 1, ph = kh / 2, pw = kw / 2, Cin % 128 == 0 (anything else of these:
+ *     YUME_EUNSUP); To = Tin, Ho = Hin, Wo = Win >= 1 (a tile of 256 positions never spans two frames; a frame smaller than a tile is legal),
+ *     Cout % 4 == 0, ldc % 16 == 0, ldc >= Cin, lde % 4 == 0, lde >= Cin / 32, ldw % 16 == 0, ldw >= kt*kh*kw*Cin, ldo % 4 == 0, ldo >= Cout,
+ *     ADD: add non-NULL, ldadd % 4 == 0, ldadd >= Cout; xq / cacheq / Wq / out / add / zero_page / sw / bias 16-byte aligned, xe / cachee 4-byte
+ *     aligned; Hin*Win*ldc < 2^31 (YUME_EINVAL). Nothing is launched when a check fails. YUME_CONV_LOG=1: one line `[conv3d_cl] f8mx M= Cin= ...`.
+ *     Accuracy: tests/conv_f8_cases.py bounds every element against fp64 on the very bytes the call receives. */
+int yume_vae_rmsnorm_silu_mx(const void* x, int64_t ldx, int64_t M, int64_t C, const float* gamma, const float* beta,
+                             int silu, void* q, int64_t ldq, void* e_out, int64_t lde, void* stream);
+int yume_conv3d_cl_f8mx(const void* xq, const void* xe, const void* cacheq, const void* cachee, int64_t ldc, int64_t lde,
+                        int64_t Tin, int64_t Hin, int64_t Win, int64_t Cin, const void* Wq, int64_t ldw, const float* sw,
+                        const float* bias, int64_t Cout, int kt, int kh, int kw, int st, int sh, int sw_, int pt, int ph, int pw,
+                        int ups, int64_t To, int64_t Ho, int64_t Wo, int epi, void* out, int64_t ldo,
+                        const void* add, int64_t ldadd, const void* zero_page, void* stream);
+
 /* ---- post-decode frame conversion ---------------------------------------------------------------
  * replaces: fastvideo/sample/sample_5b.py:491-500 save_video -> diffusers==0.32.0 VideoProcessor.postprocess_video
  *           (denormalize `(x * 0.5 + 0.5).clamp(0, 1)`, then numpy_to_pil `(x * 255).round().astype("uint8")`) — the

@@ -58,6 +58,60 @@ def rmsnorm_silu(x, gamma, silu, out, beta=None):
     return out
 
 
+def _cl8(t, name):
+    _dev(t, name, torch.uint8)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise RuntimeError(f"yume_amd.vae: {name} must be a contiguous uint8 [T,H,W,C] tensor, got {tuple(t.shape)}")
+    return t
+
+
+def rmsnorm_silu_mx(x, gamma, silu, q, e, beta=None):
+    """(q u8 [T,H,W,C], e u8 [T,H,W,C/32]) = the MX e4m3 quantisation of rmsnorm_silu(x), in one kernel, bit for bit (yume_hip.h)."""
+    lib = _lib.load()
+    _cl(x, "x")
+    _cl8(q, "q")
+    _cl8(e, "e")
+    C = x.shape[3]
+    M = x.numel() // C
+    if tuple(q.shape) != tuple(x.shape) or tuple(e.shape) != tuple(x.shape[:3]) + (C // 32,) or C % 32:
+        raise RuntimeError(f"yume_amd.vae.rmsnorm_silu_mx: x {tuple(x.shape)}, q {tuple(q.shape)}, e {tuple(e.shape)} do not fit")
+    rc = lib.yume_vae_rmsnorm_silu_mx(x.data_ptr(), C, M, C, gamma.data_ptr(), _ptr(beta), 1 if silu else 0, q.data_ptr(), C,
+                                      e.data_ptr(), C // 32, _stream())
+    _lib.check(rc, "yume_vae_rmsnorm_silu_mx")
+    return q, e
+
+
+def conv3d_cl_f8mx(xq, xe, cache, wq, sw, bias, cout, k, out, epi=EPI_BF16, add=None, zero_page=None):
+    """out[T,H,W,>=cout] = the stride-1 causal convolution of MX e4m3 activations (xq u8 [T,H,W,C], xe u8 [T,H,W,C/32]) with e4m3
+    weights wq u8 [cout, >= kt*kh*kw*C] and their per-channel scales sw; cache = None or the (bytes, scales) pair of the previous chunk's
+    last two frames (yume_hip.h)."""
+    lib = _lib.load()
+    _cl8(xq, "xq")
+    _cl8(xe, "xe")
+    _dev(wq, "wq", torch.uint8)
+    _dev(sw, "sw", torch.float32)
+    T, H, W, C = xq.shape
+    if tuple(xe.shape[:3]) != (T, H, W) or tuple(out.shape[:3]) != (T, H, W) or not out.is_contiguous():
+        raise RuntimeError("yume_amd.vae.conv3d_cl_f8mx: xq, xe and out must share [T,H,W]")
+    _dev(out, "out", torch.float32 if epi == EPI_F32 else torch.bfloat16)
+    cq = ce = None
+    if cache is not None:
+        cq, ce = cache
+        _cl8(cq, "cacheq")
+        _cl8(ce, "cachee")
+        if tuple(cq.shape) != (2, H, W, C) or tuple(ce.shape) != (2, H, W, xe.shape[3]):
+            raise RuntimeError("yume_amd.vae.conv3d_cl_f8mx: the cache pair must be [2,H,W,C] and [2,H,W,C/32]")
+    ldadd = 0
+    if add is not None:
+        _cl(add, "add")
+        ldadd = add.shape[3]
+    rc = lib.yume_conv3d_cl_f8mx(xq.data_ptr(), xe.data_ptr(), _ptr(cq), _ptr(ce), C, xe.shape[3], T, H, W, C, wq.data_ptr(), wq.stride(0),
+                                 sw.data_ptr(), _ptr(bias), cout, k[0], k[1], k[2], 1, 1, 1, k[0] - 1, k[1] // 2, k[2] // 2, 0, T, H, W, epi,
+                                 out.data_ptr(), out.shape[3], _ptr(add), ldadd, zero_page.data_ptr(), _stream())
+    _lib.check(rc, "yume_conv3d_cl_f8mx")
+    return out
+
+
 def dupup_add(x, y, ft, fs, toff):
     lib = _lib.load()
     _cl(x, "x")
