@@ -313,16 +313,25 @@ def _ws_key(t):
     return (t.device.index, _stream())
 
 
-def gemm_small_m(a, w, bias, out, epi=EPI_BF16, target_blocks=256):
-    """a @ w.T for a small number of rows against a large weight (encoders): split-K over enough slices to put ~target_blocks
-    workgroups on the chip; falls back to the plain call when no split is possible or needed."""
-    M, K = a.shape
-    N = w.shape[0]
+def small_m_splits(M, N, K, target_blocks=256):
+    """The number of K slices `gemm_small_m` cuts an [M, K] x [N, K]^T product into; 1 means the plain `gemm_bf16` call. Pure
+    host arithmetic (no device, no tensors): tests derive the route of every encoder linear from it."""
     tiles = ((M + 127) // 128) * ((N + 127) // 128)
     splits = 1
     while splits < 16 and tiles * splits * 2 <= target_blocks and K % (splits * 2 * 64) == 0 and K // (splits * 2) >= 256:
         splits *= 2
     if splits == 1 or N % 8 or (M * N) % 4:
+        return 1
+    return splits
+
+
+def gemm_small_m(a, w, bias, out, epi=EPI_BF16, target_blocks=256):
+    """a @ w.T for a small number of rows against a large weight (encoders): split-K over enough slices to put ~target_blocks
+    workgroups on the chip; falls back to the plain call when no split is possible or needed."""
+    M, K = a.shape
+    N = w.shape[0]
+    splits = small_m_splits(M, N, K, target_blocks)
+    if splits == 1:
         return gemm_bf16(a, w, bias, out, epi, variant=2 if epi == EPI_BF16_GEGLU else 0)
     lib = _lib.load()
     _dev(a, "a", torch.bfloat16)
