@@ -540,6 +540,30 @@ int yume_conv3d_cl_f8mx(const void* xq, const void* xe, const void* cacheq, cons
                         int ups, int64_t To, int64_t Ho, int64_t Wo, int epi, void* out, int64_t ldo,
                         const void* add, int64_t ldadd, const void* zero_page, void* stream);
 
+/* ---- nearest-2x upsample + Conv2d 3x3 folded into four 2x2 convolutions (r21; a function added, no argument list changed: ABI 9) -----
+ * replaces: the `nn.Upsample(2x, nearest-exact)` + `Conv2d(3x3, padding 1)` of an upsample Resample (vae2_2.py:73-171), which
+ *           yume_conv3d_cl(ups = 1) runs with nine taps per output position. On a nearest-2x image those nine taps read 2 x 2 distinct input
+ *           positions; with the taps that share a source summed at pack time the convolution is, per output parity (e_h, e_w), a 2x2 stride-1
+ *           convolution on the input-resolution image: 4 taps instead of 9.
+ *   out[t, 2a + e_h, 2b + e_w, co] = bias[co] + sum_{th, tw < 2} sum_ci x[t, a + th - (1 - e_h), b + tw - (1 - e_w), ci] * wf[2 e_h + e_w][co][(th*2 + tw)*Cin + ci]
+ *   (input positions outside [0, Hin) x [0, Win) contribute 0); all four phases in one launch; fp32 sums walked (channel tile of 64, th, tw).
+ * x bf16 [T, Hin, Win, ldc]; wf bf16 [4, Cout, ldw] — phase 2 e_h + e_w, K ordered (th, tw, ci), the sums of the 3x3 taps
+ *   wf[e_h, e_w][co][th, tw, ci] = sum_{dh in S(e_h, th)} sum_{dw in S(e_w, tw)} W[co, ci, dh, dw], S(0, .) = ({0}, {1, 2}), S(1, .) = ({0, 1}, {2}),
+ *   rounded once to bf16 (yume_amd.vae.fold_upsample_weight); bias fp32 [Cout] or NULL; out bf16 [T, 2 Hin, 2 Win, ldo].
+ * Not bit-equal to yume_conv3d_cl(ups = 1) on W: the summed weights are rounded once more (rel-L2 1.6-1.8e-3 per convolution).
+ * Any Hin * Win (a tile of 256 input positions never spans two frames or phases; a frame smaller than a tile is legal) and any T.
+ * Columns >= Cout of an out row are not written. ldo % 8 == 0: whole 16-byte stores through an LDS image, else guarded 8-byte stores.
+ * Checks (YUME_EINVAL, the text names the argument, nothing is launched): x / wf / out non-NULL; T, Hin, Win, Cin, Cout > 0;
+ *   Cin % 64 == 0; Cout % 4 == 0; ldc % 8 == 0, ldc >= Cin; ldw % 8 == 0, ldw >= 4 Cin; ldo % 4 == 0, ldo >= Cout; x / wf / out / bias 16-byte
+ *   aligned; Hin * Win < 2^28; T * 4 * ceil(Hin Win / 256) * ceil(Cout / 256) < 2^31; one input frame inside a buffer descriptor's range
+ *   ((Hin Win + 2 Win + 2) * ldc * 2 < 0x7fffff00); 255 * ldw * 2 + 128 < 2^32.
+ * YUME_CONV_LOG=1: one line `[conv3d_cl] w4fold T= Hin= Win= Cin= Cout= tiles=` per launch. YUME_CONV_FOLD_ORDER=1 (read per call,
+ *   A/B runs): tiles walk (frame, tile, phase) instead of (frame, phase, tile); the same bits.
+ * Accuracy: tests/conv_upfold_cases.py bounds every element against fp64 on the very bytes the call receives. */
+int yume_conv_up2_fold(const void* x, int64_t ldc, int64_t T, int64_t Hin, int64_t Win, int64_t Cin,
+                       const void* wf, int64_t ldw, const float* bias, int64_t Cout,
+                       void* out, int64_t ldo, void* stream);
+
 /* ---- post-decode frame conversion ---------------------------------------------------------------
  * replaces: fastvideo/sample/sample_5b.py:491-500 save_video -> diffusers==0.32.0 VideoProcessor.postprocess_video
  *           (denormalize `(x * 0.5 + 0.5).clamp(0, 1)`, then numpy_to_pil `(x * 255).round().astype("uint8")`) — the

@@ -58,6 +58,7 @@ SIGNATURES = {
     "yume_vae_rmsnorm_silu_mx": [_P, _L, _L, _L, _P, _P, _I, _P, _L, _P, _L, _P],
     "yume_conv3d_cl_f8mx": [_P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L,
                             _I, _P, _L, _P, _L, _P, _P],
+    "yume_conv_up2_fold": [_P, _L, _L, _L, _L, _L, _P, _L, _P, _L, _P, _L, _P],
     "yume_vae_dupup_add": [_P, _L, _L, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _P],
     "yume_vae_avgdown_add": [_P, _L, _L, _L, _L, _L, _P, _L, _L, _I, _I, _P],
     "yume_softmax_rows": [_P, _L, _L, _L, _F, _P, _L, _P],

@@ -42,6 +42,39 @@ def encode_passes(T, group):
     return [(0, 1, True)] + [(1 + 4 * (i - 1), 1 + 4 * (min(nchunk, i + group) - 1), False) for i in range(1, nchunk, group)]
 
 
+def upfold_qualifies(cin, cout):
+    """Does the engine's fold_upsample option run an upsample Resample's 3x3 convolution (cin -> cout) as four 2x2 phase convolutions?
+    The only place the rule lives. It looks at the layer alone, never at the frame size or count of a call: a grouped pass and the
+    one-latent walk take the same kernel. cout < 192 (the 192 -> 96 level) keeps conv_halo_n's folded-upsample instance: a 256-wide N tile
+    would be 37 % full there."""
+    return cin % 64 == 0 and cout >= 192
+
+
+_FOLD_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # S(e, t): the 3x3 taps that phase parity e reads at 2x2 tap t
+
+
+def fold_upsample_weight(w):
+    """bf16-rounded Conv2d weight [co, ci, 3, 3] behind a nearest-2x upsample -> bf16 [4, co, 2, 2, ci]: the four 2x2 phase convolutions
+    on the input-resolution image. Phase 2 e_h + e_w computes output (2a + e_h, 2b + e_w); its tap (th, tw) reads input
+    (a + th - (1 - e_h), b + tw - (1 - e_w)) (zero outside) with the weight sum_{dh in S(e_h, th)} sum_{dw in S(e_w, tw)} w[co, ci, dh, dw],
+    S(0, .) = ({0}, {1, 2}), S(1, .) = ({0, 1}, {2}); summed in fp32 in ascending (dh, dw), rounded once to bf16 (nearest even)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise RuntimeError(f"fold_upsample_weight: expected a [co, ci, 3, 3] weight, got {tuple(w.shape)}")
+    co, ci = w.shape[:2]
+    w32 = w.float()
+    out = torch.empty((4, co, 2, 2, ci), dtype=torch.float32, device=w.device)
+    for eh in range(2):
+        for ew in range(2):
+            for th in range(2):
+                for tw in range(2):
+                    acc = None
+                    for dh in _FOLD_TAPS[eh][th]:
+                        for dw in _FOLD_TAPS[ew][tw]:
+                            acc = w32[:, :, dh, dw] if acc is None else acc + w32[:, :, dh, dw]
+                    out[2 * eh + ew, :, th, tw, :] = acc
+    return out.to(torch.bfloat16)
+
+
 class _Holder(nn.Module):
     """anonymous container; the tree of these reproduces the reference state_dict key names."""
 
@@ -74,6 +107,11 @@ class VaeEngine:
         # for preview and interactive use, to be judged on a real checkpoint. Selection looks at the layer only, never at the frame size or
         # count. Part of the pack key: toggling it repacks.
         self.fp8_conv = os.environ.get("YUME_VAE_FP8", "0") == "1"
+        # r21 (env YUME_VAE_UPFOLD=1, off by default): the decoder's nearest-2x + Conv2d 3x3 of every upsample Resample that
+        # upfold_qualifies runs as four 2x2 phase convolutions on the input-resolution image (V.conv_up2_fold; weights summed and rounded
+        # to bf16 at pack time, fold_upsample_weight): 4 taps instead of 9. Not bit-equal to the 9-tap path (the summed weights are rounded
+        # once more, 1.6-1.8e-3 rel-L2 per convolution). Independent of fp8_conv. Part of the pack key: toggling it repacks.
+        self.fold_upsample = os.environ.get("YUME_VAE_UPFOLD", "0") == "1"
 
     # ------------------------------------------------------------------ weights
     def _pack(self):
@@ -107,6 +145,12 @@ class VaeEngine:
                     sw = torch.empty(cop, dtype=torch.float32, device=dev)
                     ops.quant_rows_e4m3(P[name]["w"][:, :K], wq, sw)
                     P[name].update(wq=wq, sw=sw)
+                if (self.fold_upsample and name.startswith("decoder.") and name.endswith(".resample.1") and (kt, kh, kw) == (1, 3, 3)
+                        and upfold_qualifies(ci, co)):
+                    # the four 2x2 phase convolutions of nearest-2x + 3x3: bf16 [4, cop, 4 ci], K ordered (th, tw, ci)
+                    wf = torch.zeros((4, cop, 4 * ci), dtype=torch.bfloat16, device=dev)
+                    wf[:, :co] = fold_upsample_weight(w[:, :, 0].to(torch.bfloat16)).reshape(4, co, 4 * ci)
+                    P[name]["wf"] = wf
             elif k.endswith(".gamma"):
                 P[k] = w.float().reshape(-1).contiguous()
         self.P = P
@@ -114,7 +158,7 @@ class VaeEngine:
         self.zero = torch.zeros(64, dtype=torch.bfloat16, device=dev)
 
     def ensure_packed(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.module.parameters()) + (bool(self.fp8_conv),)
+        key = tuple((p.data_ptr(), p._version) for p in self.module.parameters()) + (bool(self.fp8_conv), bool(self.fold_upsample))
         if key != self._key:
             self._pack()
             self._key = key
@@ -254,6 +298,10 @@ class VaeEngine:
             x, T = y, 2 * T
         p = self.P[name + ".resample.1"]
         out = self._new(T, 2 * H, 2 * W, _ru(p["co"], 8))
+        if "wf" in p:
+            if out.shape[3] != p["cop"]:
+                out.zero_()
+            return V.conv_up2_fold(x, p["wf"], p["b"], p["cop"], out)
         V.conv3d_cl(x, None, p["w"], p["b"], p["cop"], (1, 3, 3), (1, 1, 1), (0, 1, 1), True, out, V.EPI_BF16, zero_page=self.zero)
         return out
 

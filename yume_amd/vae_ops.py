@@ -112,6 +112,24 @@ def conv3d_cl_f8mx(xq, xe, cache, wq, sw, bias, cout, k, out, epi=EPI_BF16, add=
     return out
 
 
+def conv_up2_fold(x, wf, bias, cout, out, cin=None):
+    """out[T,2H,2W,>=cout] = Conv2d 3x3 (pad 1) of the nearest-2x upsampled x [T,H,W,C] as four 2x2 phase convolutions: wf bf16
+    [4, cout, >= 4*cin], phase 2 e_h + e_w, K ordered (th, tw, ci) (yume_amd.vae.fold_upsample_weight; yume_hip.h)."""
+    lib = _lib.load()
+    _cl(x, "x")
+    _cl(out, "out")
+    _dev(wf, "wf", torch.bfloat16)
+    T, H, W, C = x.shape
+    if tuple(out.shape[:3]) != (T, 2 * H, 2 * W):
+        raise RuntimeError(f"yume_amd.vae.conv_up2_fold: out {tuple(out.shape)} is not the 2x upsample of x {tuple(x.shape)}")
+    if wf.dim() != 3 or wf.shape[0] != 4 or wf.shape[1] != cout or not wf.is_contiguous():
+        raise RuntimeError(f"yume_amd.vae.conv_up2_fold: wf must be a contiguous [4, cout, >= 4*cin] tensor, got {tuple(wf.shape)}")
+    rc = lib.yume_conv_up2_fold(x.data_ptr(), C, T, H, W, cin if cin is not None else C, wf.data_ptr(), wf.shape[2], _ptr(bias), cout,
+                                out.data_ptr(), out.shape[3], _stream())
+    _lib.check(rc, "yume_conv_up2_fold")
+    return out
+
+
 def dupup_add(x, y, ft, fs, toff):
     lib = _lib.load()
     _cl(x, "x")
