@@ -352,6 +352,42 @@ int yume_attn_fwd_batch(const void* Q, int64_t ldq, const void* K, int64_t ldk, 
                         int64_t Lk_seg, int64_t k_pitch, int64_t H, float scale, int accumulate, int variant,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- FP8 self-attention, OCP MX e4m3 operands (r22; functions added, no argument list changed: ABI 9) -------------------------
+ * replaces (opt-in, DiTEngine.fp8_attn): the self-attention of a block in the single-sample forward, wan23/modules/model.py:139-162.
+ *
+ * The MX rule of all three (the one of yume_gemm_f8_mxout / yume_vae_rmsnorm_silu_mx): per block of 32 values amax = max |v|, e = the
+ * smallest integer with amax <= 448 * 2^e, scale byte e + 127 clamped below at 0, 127 for an all-zero block,
+ * q = e4m3_rne(clamp(v * 2^-e, +-448)).
+ *
+ * yume_quant_rows_mx_e4m3: x bf16 [R, K] (row stride ldx elements) -> q u8 [R, K] (row stride ldq bytes), e u8 [R, K / 32] (row stride
+ *   lde bytes), one block per row and 32 consecutive columns. Bytes beyond K / K / 32 of a row and rows beyond R are not written.
+ *   Checks (YUME_EINVAL, by name `quant_rows_mx_e4m3`): K % 32 == 0, ldx % 8 == 0, ldx >= K, ldq % 16 == 0, ldq >= K, lde >= K / 32, every
+ *   pitch below 2^31, x and q 16-byte aligned, non-NULL. R == 0: YUME_OK, nothing is launched.
+ *   One call on qk [L, 2 C] gives q8 | k8 and, per row, the 4 H scale bytes of q followed by the 4 H of k.
+ * yume_attn_vt_mx_e4m3: the bf16 K-major V^T image Vt [C, Lk] (row stride ldvt elements) -> the e4m3 image Vt8 [C, 128 * tiles]
+ *   (row stride ldvt8 bytes), tiles = ceil(Lk / 128), and Ev u8 [tiles, 4 * C] (row stride ldev bytes):
+ *       Vt8[c, 128 t + kk] = key 128 t + key_of(kk),   key_of(kk) = 16 w + 4 g + y with g = (kk >> 4) & 3, w = 4 (kk >> 6) + ((kk >> 2) & 3),
+ *       y = kk & 3;     Ev[t, 4 c + b] = the scale byte of bytes kk = 32 b .. 32 b + 31 of that tile row
+ *   (the order in which the kernel's P operand holds its keys: yume_amd/csrc/quant_mx.hip). Keys >= Lk of the last tile are written as
+ *   byte 0x00 under a valid scale byte: the caller never clears anything. Columns of Vt at or beyond Lk are never read.
+ *   Checks (by name `attn_vt_mx_e4m3`): C % 128 == 0, C < 65536, Lk >= 1, ldvt % 4 == 0, ldvt >= Lk, ldvt8 % 16 == 0, ldvt8 >= 128 * tiles,
+ *   ldev % 4 == 0, ldev >= 4 * C, every pitch below 2^31, Vt 8-byte, Vt8 16-byte, Ev 4-byte aligned, non-NULL.
+ * yume_attn_fwd_f8mx: O[i, 128 h + d] = sum_j 2^<q^_i, k^_j> v^_jd / sum_j 2^<q^_i, k^_j> over j < Lk, the hatted operands the dequantised
+ *   bytes (the scale and log2(e) are already in q: yume_rmsnorm_rope's q). Q8 u8 [Lq, 128 H] (ldq bytes), Eq u8 [Lq, 4 H] (ldeq),
+ *   K8 u8 [Lk, 128 H] (ldk), Ek u8 [Lk, 4 H] (ldek), Vt8 / Ev as above with C = 128 H, O bf16 [Lq, 128 H] (ldo elements). head_dim 128,
+ *   any Lq >= 1 and Lk >= 1. Both products run on v_mfma_scale_f32_16x16x128_f8f6f4; the probabilities are rounded once to e4m3 after
+ *   a multiplication by 2^8 (p below 2^-18 of the row's running maximum is dropped), the row sum is taken over the unrounded ones.
+ *   No accumulate, weighted key, workspace or key split. Rows of O beyond Lq and columns beyond 128 H are not written.
+ *   Checks (by name `attn_fwd_f8mx`): non-NULL; Lq, Lk, H >= 1; ldq / ldk % 16 == 0 and >= 128 H; ldeq / ldek % 4 == 0 and >= 4 H;
+ *   ldvt8 % 16 == 0 and >= 128 * tiles; ldev % 4 == 0 and >= 512 H; ldo % 4 == 0 and >= 128 H; every pitch below 2^31 (the kernel's
+ *   addressing); Q8, K8, Vt8, O 16-byte, Eq, Ek, Ev 4-byte aligned.
+ * env YUME_ATTN_LOG=1: `[attn] f8mx Lq=.. Lk=.. H=.. tiles=..` per launch; YUME_NORM_LOG=1: `[quant] rows_mx ...` / `[quant] vt_mx ...`. */
+int yume_quant_rows_mx_e4m3(const void* x, int64_t ldx, int64_t R, int64_t K, void* q, int64_t ldq, void* e, int64_t lde, void* stream);
+int yume_attn_vt_mx_e4m3(const void* Vt, int64_t ldvt, int64_t C, int64_t Lk, void* Vt8, int64_t ldvt8, void* Ev, int64_t ldev, void* stream);
+int yume_attn_fwd_f8mx(const void* Q8, int64_t ldq, const void* Eq, int64_t ldeq, const void* K8, int64_t ldk, const void* Ek, int64_t ldek,
+                       const void* Vt8, int64_t ldvt8, const void* Ev, int64_t ldev, void* O, int64_t ldo,
+                       int64_t Lq, int64_t Lk, int64_t H, void* stream);
+
 /* ---- small-M fp32 linear (time embedding MLP) ---------------------------------------------
  * replaces: wan23/modules/model.py:459-461,803-812 (time_embedding, time_projection under
  *           autocast(float32)); only R distinct timesteps are evaluated (R <= 8).

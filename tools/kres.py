@@ -3,9 +3,11 @@
 import re, subprocess, sys, os, glob
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 files = sys.argv[1:] or sorted(glob.glob(os.path.join(root, "yume_amd/csrc/*.hip")))
+sys.path.insert(0, root)
+from yume_amd.build import EXTRA_FLAGS          # the per-file flags of the product build
 for f in files:
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "-DNDEBUG",
-                        "-I", os.path.join(root, "include"), "-c", f, "-o", "/dev/null",
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "-DNDEBUG"] + EXTRA_FLAGS.get(os.path.basename(f), []) +
+                       ["-I", os.path.join(root, "include"), "-c", f, "-o", "/dev/null",
                         "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     cur = {}
     for line in r.stderr.splitlines():

@@ -45,6 +45,9 @@ SIGNATURES = {
     "yume_attn_fwd_seg": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _F, _I, _I, _P, _P],
     "yume_attn_batch_workspace_bytes": [_L, _L, _L, _L],
     "yume_attn_fwd_batch": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _L, _L, _F, _I, _I, _P, _L, _P],
+    "yume_quant_rows_mx_e4m3": [_P, _L, _L, _L, _P, _L, _P, _L, _P],
+    "yume_attn_vt_mx_e4m3": [_P, _L, _L, _L, _P, _L, _P, _L, _P],
+    "yume_attn_fwd_f8mx": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P],
     "yume_linear_smallm_f32": [_P, _L, _L, _P, _I, _P, _L, _I, _I, _P, _P, _P],
     "yume_sinusoidal_embed": [_P, _P, _L, _L, _P, _P],
     "yume_modulation_table": [_P, _P, _L, _L, _L, _P, _P],

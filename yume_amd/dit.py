@@ -97,6 +97,13 @@ class DiTEngine:
         # (norm3) -> gemm_f8 (_qkv_step, _cross_q_step). o and cross-o stay bf16 (their input is the attention output). Independent of the two
         # FFN options. Off by default = the bf16 calls, bit for bit; env YUME_FP8_QKV=1 turns it on. Part of the pack key: flipping it re-packs.
         self.fp8_qkv = os.environ.get("YUME_FP8_QKV", "0") == "1"
+        # r22: the self-attention of the single-sample forward (_blocks and its trimmed last block) on MX e4m3 operands: behind rmsnorm_rope one
+        # quantiser pass over qk [L, 2C], one over the V^T image, then yume_attn_fwd_f8mx (_self_attn_step). Cross-attention, forward_cfg /
+        # forward_pair, forward_batch, the sequence-parallel path, a head_dim other than 128, YUME_ATTN_PRESCALE=0 and the cross-check variants
+        # keep the bf16 calls (said once on stderr under YUME_ATTN_LOG=1). Independent of the other FP8 options; no weight is repacked, so it
+        # is not part of the pack key. Off by default = the bf16 calls, bit for bit; env YUME_FP8_ATTN=1 turns it on.
+        self.fp8_attn = os.environ.get("YUME_FP8_ATTN", "0") == "1"
+        self._fp8_attn_said = set()
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -397,10 +404,9 @@ class DiTEngine:
                 ops.rmsnorm_rope(qk[:n_rope], C, 2, d["nqk"], self.qk_eps, rope)
                 ops.rmsnorm_rope(qk[n_rope:], C, 2, d["nqk"], self.qk_eps, None)
             if self.sp is None:
-                T("attn_self", ops.attn_fwd, qk[:, :C], qk[:, C:], vt, att, L, n_keys if n_keys is not None else L, H, variant=self.attn_variant,
-                  q_prescaled=self.q_prescale, kv_padded=True)
-                sa = att
+                sa = self._self_attn_step(qk, vt, att, 0, L, n_keys if n_keys is not None else L)
             else:      # Ulysses: all tokens x this rank's heads, then back (2 collectives, yume_amd/ulysses.py)
+                self._fp8_attn_notice("the sequence-parallel self-attention keeps the bf16 kernels")
                 qf, kf, vtf = self.sp.exchange_qkv(qk, vt, C)
                 of = self._buf("att_sp", (qf.shape[0], qf.shape[1]), torch.bfloat16)
                 ops.attn_fwd(qf, kf, vtf, of, qf.shape[0], n_keys, H // self.sp.world, variant=self.attn_variant, q_prescaled=self.q_prescale)
@@ -419,6 +425,40 @@ class DiTEngine:
             self._ffn_block(d, xs, h, ff, scale_ff, shift_ff, gate_ff, ts, row_idx, eps)
             if cache is not None and cache[0] == "record" and i in cache[1]:
                 cache[2].append((xs - x_in).to(torch.bfloat16).unsqueeze(0))     # reference keeps [B, L, C] bf16
+
+    def _fp8_attn_notice(self, why):
+        """one stderr line per reason and engine (YUME_ATTN_LOG=1), in the style of the [fp8_qkv] notices"""
+        if self.fp8_attn and why not in self._fp8_attn_said:
+            self._fp8_attn_said.add(why)
+            if os.environ.get("YUME_ATTN_LOG", "0") not in ("", "0"):
+                sys.stderr.write(f"[fp8_attn] {why}\n")
+
+    def _self_attn_step(self, qk, vt, out, s, L, n_keys):
+        """the self-attention of one block of the single-sample forward behind rmsnorm_rope: the queries are the rows [s, L) of qk[:, :C], the
+        keys the first n_keys rows of qk[:, C:] and columns of vt; out [L - s, C]. With fp8_attn: quant_rows_mx(qk) + attn_vt_mx(vt) ->
+        attn_fwd_f8mx on engine-owned byte buffers (allocated by the first eager forward); otherwise today's bf16 call."""
+        m = self.model
+        C, H = m.dim, m.num_heads
+        T = self._timed
+        if self.fp8_attn:
+            if C != 128 * H:
+                self._fp8_attn_notice(f"self-attention stays bf16: head_dim={C // H} is not 128")
+            elif not self.q_prescale or self.attn_variant != 0:
+                self._fp8_attn_notice("self-attention stays bf16: the e4m3 kernel takes pre-scaled q and the automatic variant only")
+            else:
+                self._fp8_attn_notice("cross-attention keeps the bf16 kernels")
+                nt = (n_keys + 127) // 128
+                qk8 = self._buf("qk8", (L, 2 * C), torch.uint8)
+                qke = self._buf("qke", (L, 8 * H), torch.uint8)
+                vt8 = self._buf("vt8", (C, 128 * nt), torch.uint8)
+                ev = self._buf("vt8e", (nt, 4 * C), torch.uint8)
+                T("quant_mx", ops.quant_rows_mx_e4m3, qk[:L], qk8, qke)
+                T("quant_mx", ops.attn_vt_mx_e4m3, vt, n_keys, vt8, ev)
+                T("attn_self", ops.attn_fwd_f8mx, qk8[s:, :C], qke[s:, :4 * H], qk8[:, C:], qke[:, 4 * H:], vt8, ev, out, L - s, n_keys, H)
+                return out
+        T("attn_self", ops.attn_fwd, qk[s:, :C], qk[:, C:], vt, out, L - s, n_keys, H, variant=self.attn_variant, q_prescaled=self.q_prescale,
+          kv_padded=True)
+        return out
 
     def _qkv_step(self, d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps):
         """the first adaLN of a block and its QKV projection, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike: q | k into
@@ -507,7 +547,7 @@ class DiTEngine:
         n = L - s
         self._qkv_step(d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps)
         T("rmsnorm_rope", ops.rmsnorm_rope, qk, C, 2, d["nqk"], self.qk_eps, rope)
-        T("attn_self", ops.attn_fwd, qo, qk[:, C:], vt, ao, n, L, H, variant=self.attn_variant, q_prescaled=self.q_prescale, kv_padded=True)
+        self._self_attn_step(qk, vt, ao, s, L, L)
         T("gemm_o", ops.gemm_bf16, ao, d["wo"], d["bo"], xo, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ro, variant=self.gemm_variant)
         self._cross_q_step(d, xo, ho, qo, eps)
         T("rmsnorm_rope", ops.rmsnorm_rope, qo, C, 1, d["nq_c"], self.qk_eps)
@@ -776,6 +816,7 @@ class DiTEngine:
         m = self.model
         C, H, Fd, eps = m.dim, m.num_heads, m.ffn_dim, m.eps
         M = pitch + L
+        self._fp8_attn_notice("forward_pair / forward_cfg keep the bf16 self-attention kernels")
         # rows and V^T columns exist up to a whole key tile behind leg 1 as well (zeros nobody writes): YUME_ATTN_KV_PADDED per leg
         h = self._buf("h_p", (M, C), torch.bfloat16)
         qk = self._buf("qk_p", (2 * pitch, 2 * C), torch.bfloat16, zero=True)
@@ -943,6 +984,7 @@ class DiTEngine:
         m = self.model
         C, H, Fd, eps = m.dim, m.num_heads, m.ffn_dim, m.eps
         M = (B - 1) * pitch + L
+        self._fp8_attn_notice("forward_batch keeps the bf16 self-attention kernels")
         # rows and V^T columns exist up to a whole key tile behind the last sample as well (zeros nobody writes): YUME_ATTN_KV_PADDED per sample
         h = self._buf("h_b", (M, C), torch.bfloat16)
         qk = self._buf("qk_b", (B * pitch, 2 * C), torch.bfloat16, zero=True)

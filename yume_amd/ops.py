@@ -533,6 +533,68 @@ def attn_fwd_batch(q, k, vt, out, nseg, Lq_seg, q_pitch, Lk_seg, k_pitch, H, sca
     return out
 
 
+def quant_rows_mx_e4m3(x, q, e):
+    """OCP MX quantiser (yume_quant_rows_mx_e4m3): x bf16 [R, K] -> q u8 [R, K] e4m3 bytes, e u8 [R, K / 32] E8M0 scale bytes, one per row
+    and 32 consecutive columns."""
+    lib = _lib.load()
+    _dev(x, "x", torch.bfloat16)
+    _dev(q, "q", torch.uint8)
+    _dev(e, "e", torch.uint8)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    ep, lde = _rows(e, "e")
+    R, K = x.shape
+    if tuple(q.shape) != (R, K) or tuple(e.shape) != (R, K // 32):
+        raise RuntimeError(f"yume_amd.quant_rows_mx_e4m3: x {tuple(x.shape)}, q {tuple(q.shape)}, e {tuple(e.shape)} do not fit")
+    rc = lib.yume_quant_rows_mx_e4m3(xp, ldx, R, K, qp, ldq, ep, lde, _stream())
+    _lib.check(rc, "yume_quant_rows_mx_e4m3")
+    return q, e
+
+
+def attn_vt_mx_e4m3(vt, Lk, vt8, ev):
+    """The e4m3 V^T image of attn_fwd_f8mx (yume_attn_vt_mx_e4m3): vt bf16 [C, >= Lk] K-major -> vt8 u8 [C, >= 128 * tiles] in the kernel's key
+    order, ev u8 [tiles, >= 4 * C], tiles = ceil(Lk / 128); keys >= Lk of the last tile are written as zeros."""
+    lib = _lib.load()
+    _dev(vt, "vt", torch.bfloat16)
+    _dev(vt8, "vt8", torch.uint8)
+    _dev(ev, "ev", torch.uint8)
+    vp, ldvt = _rows(vt, "vt")
+    v8p, ldvt8 = _rows(vt8, "vt8")
+    evp, ldev = _rows(ev, "ev")
+    C = vt.shape[0]
+    tiles = (Lk + 127) // 128
+    if vt.shape[1] < Lk or vt8.shape[0] != C or vt8.shape[1] < 128 * tiles or ev.shape[0] < tiles or ev.shape[1] < 4 * C:
+        raise RuntimeError(f"yume_amd.attn_vt_mx_e4m3: vt {tuple(vt.shape)}, vt8 {tuple(vt8.shape)}, ev {tuple(ev.shape)} do not fit Lk={Lk}")
+    rc = lib.yume_attn_vt_mx_e4m3(vp, ldvt, C, Lk, v8p, ldvt8, evp, ldev, _stream())
+    _lib.check(rc, "yume_attn_vt_mx_e4m3")
+    return vt8, ev
+
+
+def attn_fwd_f8mx(q8, eq, k8, ek, vt8, ev, out, Lq, Lk, H):
+    """out[Lq, H*128] bf16 = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j) over MX e4m3 operands (yume_attn_fwd_f8mx): q8 / k8 u8 token-major 2-D views
+    with their scale bytes eq / ek [rows, >= 4 H] (quant_rows_mx_e4m3), vt8 / ev from attn_vt_mx_e4m3. q already carries scale * log2(e)."""
+    lib = _lib.load()
+    for t, name in ((q8, "q8"), (eq, "eq"), (k8, "k8"), (ek, "ek"), (vt8, "vt8"), (ev, "ev")):
+        _dev(t, name, torch.uint8)
+    _dev(out, "out", torch.bfloat16)
+    qp, ldq = _rows(q8, "q8")
+    eqp, ldeq = _rows(eq, "eq")
+    kp, ldk = _rows(k8, "k8")
+    ekp, ldek = _rows(ek, "ek")
+    vp, ldvt8 = _rows(vt8, "vt8")
+    evp, ldev = _rows(ev, "ev")
+    op, ldo = _rows(out, "out")
+    tiles = (Lk + 127) // 128
+    if (q8.shape[0] < Lq or eq.shape[0] < Lq or k8.shape[0] < Lk or ek.shape[0] < Lk or out.shape[0] < Lq or vt8.shape[0] < H * 128
+            or vt8.shape[1] < 128 * tiles or ev.shape[0] < tiles or min(q8.shape[1], k8.shape[1], out.shape[1]) < H * 128
+            or min(eq.shape[1], ek.shape[1]) < 4 * H or ev.shape[1] < 512 * H):
+        raise RuntimeError(f"yume_amd.attn_fwd_f8mx: operands do not fit Lq={Lq} Lk={Lk} H={H}: q8 {tuple(q8.shape)} eq {tuple(eq.shape)} "
+                           f"k8 {tuple(k8.shape)} ek {tuple(ek.shape)} vt8 {tuple(vt8.shape)} ev {tuple(ev.shape)} out {tuple(out.shape)}")
+    rc = lib.yume_attn_fwd_f8mx(qp, ldq, eqp, ldeq, kp, ldk, ekp, ldek, vp, ldvt8, evp, ldev, op, ldo, Lq, Lk, H, _stream())
+    _lib.check(rc, "yume_attn_fwd_f8mx")
+    return out
+
+
 def linear_smallm_f32(x, w, bias, out, in_act=0, out_act=0, add_table=None):
     lib = _lib.load()
     _dev(x, "x", torch.float32)
