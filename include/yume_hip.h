@@ -118,7 +118,8 @@ enum {
     YUME_EPI_BF16_SPLITT = 4,
     YUME_EPI_BF16_GELU_ERF = 5,
     YUME_EPI_BF16_GEGLU = 6,     /* see the T5 section below */
-    YUME_EPI_MX_GELU = 7         /* yume_gemm_f8_mxout only: e4m3 bytes + one E8M0 scale byte per 32 columns (the FP8 FFN section) */
+    YUME_EPI_MX_GELU = 7,        /* yume_gemm_f8_mxout only: e4m3 bytes + one E8M0 scale byte per 32 columns (the FP8 FFN section) */
+    YUME_EPI_MX6_GELU = 8        /* yume_gemm_f6_mxout only: packed e2m3 + one E8M0 scale byte per 32 columns (the MXFP6 FFN section) */
 };
 int yume_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
                    int64_t M, int64_t N, int64_t K, int epi,
@@ -208,6 +209,42 @@ int yume_gemm_f8_mxout(const void* Aq, int64_t lda, const float* sa, const void*
 int yume_gemm_f8_mx(const void* Aq, int64_t lda, const void* ea, int64_t ldea, const void* Wq, int64_t ldw, const float* sw,
                     const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
                     const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
+
+/* ---- MXFP6 (OCP e2m3) FFN linears (r23; functions added, no argument list changed: ABI 9) ----------------------------------
+ * replaces (opt-in, DiTEngine.fp6_ffn): the FFN adaLN and the two FFN linears of a block, wan23/modules/model.py:265-267,309-312.
+ *
+ * The format, once: e2m3 = 1 sign, 2 exponent bits (bias 1), 3 mantissa bits, no inf / nan; largest value 7.5, subnormal step 0.125.
+ * 32 values pack into 24 bytes, value i at bits [6 i, 6 i + 6) of the group, little-endian: a row of K values is 3 K / 4 bytes. One
+ * E8M0 byte per row and 32 consecutive k: e = the smallest integer with amax <= 7.5 * 2^e, byte e + 127 clamped below at 0, 127 for an
+ * all-zero block (the project's MX rule with 7.5 in place of 448); q = e2m3_rne(clamp(v * 2^-e, +-7.5)).
+ *
+ * yume_adaln_modulate_mx_e2m3: yume_adaln_modulate(..., out_kind = 0) followed by that quantiser on its bf16 output, in one kernel and
+ *   without the bf16 row: q u8 [T, 3 C / 4] (row stride ldq bytes) and e u8 [T, C / 32] (row stride lde) equal the two-step composite
+ *   bit for bit. Checks (YUME_EINVAL): C % 32 == 0, C <= 8192, ldq % 16 == 0, ldq >= 3 C / 4, lde % 16 == 0, lde >= C / 32, ldx % 4 == 0,
+ *   tab_stride % 4 == 0, q 16-byte aligned. Bytes beyond 3 C / 4 of a q row, scale bytes beyond C / 32 and rows beyond T are not
+ *   written. T == 0: YUME_OK, nothing is launched. YUME_NORM_LOG=1: `[norm] adaln_e2m3<MAXV> ...` / `[norm] adaln2_e2m3 ...`.
+ * yume_gemm_f6_mx (the consumer): acc[m, n] = sum_b 2^(ea[m, b] - 127) 2^(ew[n, b] - 127) sum_{k in block b} A[m, k] W[n, k], both block
+ *   scales applied by v_mfma_scale_f32_16x16x128_f8f6f4 itself (maps: profiles/r23_fp6_ffn.md); y = acc + bias[n]; then YUME_EPI_F32 or
+ *   YUME_EPI_RESID with out, ldo, gate, gate_stride, row_idx as in yume_gemm_bf16_ws (any other epilogue: YUME_EUNSUP).
+ *   A6 u8 [M, 3 K / 4] (lda bytes), ea u8 [M, K / 32] (ldea), W6 u8 [N, 3 K / 4] (ldw), ew u8 [N, K / 32] (ldew), bias fp32 [N] or NULL.
+ *   Checks (YUME_EINVAL): K % 128 == 0, N % 4 == 0, lda / ldw % 16 == 0 and >= 3 K / 4, ldea / ldew % 16 == 0 and >= K / 32 (a row's
+ *   scale bytes are read in whole 16-byte groups: up to 15 bytes behind K / 32 inside the pitch are read, never used), ldo % 4 == 0,
+ *   every pointer 16-byte aligned, gate_stride % 4 == 0. M >= 1, N >= 1 otherwise arbitrary. One 256 x 256 tile per workgroup.
+ * yume_gemm_f6_mxout (the producer; epi must be YUME_EPI_MX6_GELU, anything else YUME_EUNSUP): the same operands and sum;
+ *   v = gelu_tanh(acc + bias[n]) in fp32 leaves quantised by the rule above: out u8 [M, 3 N / 4] (ldo bytes), eo u8 [M, N / 32] (ldeo).
+ *   Checks: those of yume_gemm_f6_mx on the operands and N % 128 == 0, ldo % 16 == 0, ldo >= 3 N / 4, ldeo % 16 == 0, ldeo >= N / 32
+ *   (the output is the next call's A operand). Rows beyond M, bytes beyond 3 N / 4 and scale bytes beyond N / 32 are not written.
+ * Accuracy of the sum: tests/gemm_f6_cases.py bounds every element against fp64 on the very bytes the call receives.
+ * YUME_GEMM_LOG=1: `[gemm_f6] mx ...` / `[gemm_f6] mxout ...` per launch. */
+int yume_adaln_modulate_mx_e2m3(const float* x, int64_t ldx, int64_t T, int64_t C, float eps, const float* mul,
+                                const float* add, int64_t tab_stride, const int32_t* row_idx, int add_one,
+                                void* q, int64_t ldq, void* e, int64_t lde, void* stream);
+int yume_gemm_f6_mx(const void* A6, int64_t lda, const void* ea, int64_t ldea, const void* W6, int64_t ldw, const void* ew, int64_t ldew,
+                    const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
+                    const float* gate, int64_t gate_stride, const int32_t* row_idx, void* stream);
+int yume_gemm_f6_mxout(const void* A6, int64_t lda, const void* ea, int64_t ldea, const void* W6, int64_t ldw, const void* ew, int64_t ldew,
+                       const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
+                       void* eo, int64_t ldeo, void* stream);
 
 /* ---- RMSNorm over the hidden dim (+ optional 3D RoPE), in place, bf16 -----------------------
  * replaces: wan23/modules/model.py:121-137 (WanRMSNorm on q,k over the FULL hidden dim C),

@@ -104,6 +104,13 @@ class DiTEngine:
         # is not part of the pack key. Off by default = the bf16 calls, bit for bit; env YUME_FP8_ATTN=1 turns it on.
         self.fp8_attn = os.environ.get("YUME_FP8_ATTN", "0") == "1"
         self._fp8_attn_said = set()
+        # r23: the FFN adaLN and both FFN linears of every block whose dim and ffn_dim are multiples of 128 in OCP MXFP6 e2m3, BOTH operands of
+        # both GEMMs with one E8M0 scale byte per row and 32 k: adaln_modulate_mx_e2m3 -> gemm_f6_mxout (GELU, MX6 out) -> gemm_f6_mx (RESID);
+        # no quantiser pass, no bf16 ff (_ffn_block). The weights are packed once at pack time (ops.mx6_pack), the bf16 weights stay. Wins over
+        # fp8_ffn / fp8_ffn_fused where both are on. Off by default = today's path, bit for bit; env YUME_FP6_FFN=1 turns it on. Part of the
+        # pack key: flipping it re-packs.
+        self.fp6_ffn = os.environ.get("YUME_FP6_FFN", "0") == "1"
+        self._fp6_ffn_said = False
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -122,7 +129,7 @@ class DiTEngine:
     def _param_key(self):
         # walked once per forward: (storage address, in-place version, dtype) of every parameter — a load_state_dict, an
         # optimizer step or a .to(dtype) re-packs; cheap next to one forward (≈1 k tensors), and cached per forward call
-        return (self.q_prescale, bool(self.fp8_ffn), bool(self.fp8_qkv)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
+        return (self.q_prescale, bool(self.fp8_ffn), bool(self.fp8_qkv), bool(self.fp6_ffn)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
 
     def _pack(self):
         m = self.model
@@ -196,6 +203,12 @@ class DiTEngine:
                         ops.quant_rows_e4m3(d[wk], d[qk_], d[sk_])
                 elif os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
                     sys.stderr.write(f"[fp8_ffn] block {len(blocks)} keeps bf16 FFN linears: dim={C} ffn_dim={m.ffn_dim} are not both multiples of 128\n")
+            if self.fp6_ffn:
+                if C % 128 == 0 and m.ffn_dim % 128 == 0:
+                    d["w1p"], d["e1"] = ops.mx6_pack(d["w1"])
+                    d["w2p"], d["e2"] = ops.mx6_pack(d["w2"])
+                elif os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
+                    sys.stderr.write(f"[fp6_ffn] block {len(blocks)} keeps its FFN linears: dim={C} ffn_dim={m.ffn_dim} are not both multiples of 128\n")
             if self.fp8_qkv:
                 log = os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0")
                 if C % 128 == 0:       # (K % 128 == 0 and n_split = 2 C a multiple of 256: every DiT the attention kernels take, head_dim 128)
@@ -500,6 +513,22 @@ class DiTEngine:
         and 32 columns (OCP MX; no bf16 ff is written), and ffn.2 consumes those scales inside the MFMA. Everything is row-local; the byte and
         scale buffers are workspaces, allocated by the first eager forward."""
         T = self._timed
+        if self.fp6_ffn and "w1p" in d:
+            # (r23) MXFP6 e2m3, in front of the fp8 branch: adaLN emits packed e2m3 rows + E8M0 bytes, ffn.0's GELU epilogue emits the same, ffn.2
+            # consumes them; the weights' block scales (e1 / e2) act inside the MFMA too. Row-local; the buffers are workspaces, allocated by the
+            # first eager forward. Scale buffers have a pitch of whole 16-byte groups.
+            if (self.fp8_ffn or self.fp8_ffn_fused) and not self._fp6_ffn_said and os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
+                sys.stderr.write("[fp6_ffn] fp8_ffn is on too: the qualifying blocks run the MXFP6 FFN\n")
+                self._fp6_ffn_said = True
+            n, Cc, F = h.shape[0], h.shape[1], ff.shape[1]
+            h6 = self._buf("ffn6_h", (n, 3 * Cc // 4), torch.uint8, grow_rows=True)
+            he = self._buf("ffn6_he", (n, (Cc // 32 + 15) // 16 * 16), torch.uint8, grow_rows=True)[:, :Cc // 32]
+            f6 = self._buf("ffn6_f", (n, 3 * F // 4), torch.uint8, grow_rows=True)
+            fe = self._buf("ffn6_fe", (n, (F // 32 + 15) // 16 * 16), torch.uint8, grow_rows=True)[:, :F // 32]
+            T("adaln", ops.adaln_modulate_mx_e2m3, xs, scale_ff, shift_ff, ts, row_idx, True, h6, he, eps)
+            T("gemm_ffn0", ops.gemm_f6_mxout, h6, he, d["w1p"], d["e1"][:, :Cc // 32], d["b1"], f6, fe)
+            T("gemm_ffn2", ops.gemm_f6_mx, f6, fe, d["w2p"], d["e2"][:, :F // 32], d["b2"], xs, EPI_RESID, gate=gate_ff, gate_stride=ts, row_idx=row_idx)
+            return
         if not (self.fp8_ffn_fused and "w1q" in d and ff.shape[1] % 32 == 0):
             T("adaln", ops.adaln_modulate, xs, scale_ff, shift_ff, ts, row_idx, True, h, 0, eps)
             self._ffn(d, h, ff, xs, gate_ff, ts, row_idx)

@@ -304,6 +304,104 @@ def gemm_f8_mx(aq, ea, wq, sw, bias, out, epi=EPI_F32, gate=None, gate_stride=0,
     return out
 
 
+# ---- (r23) OCP MXFP6 e2m3: packed values (32 per 24 bytes, value i at bits [6 i, 6 i + 6)) + one E8M0 byte per row and 32 k (yume_hip.h)
+EPI_MX6_GELU = 8
+E2M3_MAX = 7.5
+
+
+def _ceil16(v):
+    return (v + 15) // 16 * 16
+
+
+def mx6_pack(w):
+    """the host packer: w [N, K] (bf16 or any float, K % 32 == 0) -> (packed u8 [N, 3 K / 4], scale bytes u8 [N, round_up(K / 32, 16)] of which
+    [:, :K / 32] are the scales, the rest 127). In torch on w's device; runs once, when the engine packs. Per row and 32 consecutive k:
+    e = the smallest integer with amax <= 7.5 * 2^e (byte e + 127 clamped below at 0; 127 for a zero block), code = e2m3_rne(clamp(w * 2^-e,
+    +-7.5)) with the sign bit of every w < 0."""
+    N, K = w.shape
+    if K % 32:
+        raise RuntimeError(f"yume_amd.mx6_pack: K={K} must be a multiple of 32")
+    x = w.detach().float()
+    amax = x.abs().view(N, K // 32, 32).amax(dim=2)
+    m, ex = torch.frexp(amax)                                      # amax = m 2^ex, m in [0.5, 1): 1.f = 2 m
+    e = ex - 1 - 2 + (2 * m > 1.875).int()
+    byte = torch.where(amax > 0, (e + 127).clamp(min=0), torch.full_like(e, 127))
+    mult = torch.pow(2.0, 127 - byte.double()).repeat_interleave(32, dim=1)
+    t = (x.double() * mult).clamp(-E2M3_MAX, E2M3_MAX)
+    a = t.abs()
+    step = torch.pow(2.0, torch.floor(torch.log2(a.clamp(min=1.0))) - 3)       # 1/8 below 2, 1/4 in [2, 4), 1/2 from 4
+    r = torch.round(a / step) * step                                # torch.round: half to even
+    ex2 = torch.floor(torch.log2(r.clamp(min=1.0)))
+    code = torch.where(r < 1.0, r * 8, (ex2 + 1) * 8 + (r / torch.pow(2.0, ex2) - 1) * 8).to(torch.int64) | ((t < 0).to(torch.int64) << 5)
+    c = code.view(N, K // 4, 4)
+    word = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)            # four values = three bytes
+    packed = torch.stack([word & 255, (word >> 8) & 255, (word >> 16) & 255], dim=2).to(torch.uint8).view(N, 3 * K // 4).contiguous()
+    eb = torch.full((N, _ceil16(K // 32)), 127, dtype=torch.uint8, device=w.device)
+    eb[:, :K // 32] = byte.to(torch.uint8)
+    return packed, eb
+
+
+def adaln_modulate_mx_e2m3(x, mul, add, tab_stride, row_idx, add_one, q, e, eps=1e-6):
+    """q u8 [T, 3 C / 4], e u8 [T, C / 32] (a view whose row pitch is a multiple of 16) = the MX6 quantiser applied to
+    adaln_modulate(x, ..., out bf16), in one kernel, bit for bit (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(x, "x", torch.float32)
+    _dev(q, "q", torch.uint8)
+    _dev(e, "e", torch.uint8)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    ep, lde = _rows(e, "e")
+    T, C = x.shape
+    if tuple(q.shape) != (T, 3 * C // 4) or tuple(e.shape) != (T, C // 32):
+        raise RuntimeError(f"yume_amd.adaln_modulate_mx_e2m3: x {tuple(x.shape)}, q {tuple(q.shape)}, e {tuple(e.shape)} do not fit")
+    rc = lib.yume_adaln_modulate_mx_e2m3(xp, ldx, T, C, eps, mul.data_ptr(), add.data_ptr(), tab_stride, _ptr(row_idx),
+                                         1 if add_one else 0, qp, ldq, ep, lde, _stream())
+    _lib.check(rc, "yume_adaln_modulate_mx_e2m3")
+    return q, e
+
+
+def _f6_operands(who, a6, ea, w6, ew):
+    for t, name in ((a6, "a6"), (ea, "ea"), (w6, "w6"), (ew, "ew")):
+        _dev(t, name, torch.uint8)
+    M, KB = a6.shape
+    N, KB2 = w6.shape
+    K = KB * 4 // 3
+    if KB != KB2 or KB % 96:
+        raise RuntimeError(f"yume_amd.{who}: packed rows of {KB} and {KB2} bytes (equal multiples of 96 needed)")
+    if tuple(ea.shape) != (M, K // 32) or tuple(ew.shape) != (N, K // 32):
+        raise RuntimeError(f"yume_amd.{who}: scales ea {tuple(ea.shape)}, ew {tuple(ew.shape)} do not fit M={M}, N={N}, K={K}")
+    return M, N, K
+
+
+def gemm_f6_mxout(a6, ea, w6, ew, bias, out, eo, epi=EPI_MX6_GELU):
+    """the MX6 producer: out u8 [M, 3 N / 4], eo u8 [M, N / 32] = the MX6 quantiser applied to gelu_tanh(acc + bias), acc the block-scaled
+    e2m3 x e2m3 sum of yume_gemm_f6_mx (yume_hip.h). ea / ew / eo: views [rows, K / 32] / [M, N / 32] with a row pitch that is a multiple of 16."""
+    lib = _lib.load()
+    M, N, K = _f6_operands("gemm_f6_mxout", a6, ea, w6, ew)
+    _dev(out, "out", torch.uint8)
+    _dev(eo, "eo", torch.uint8)
+    if tuple(out.shape) != (M, 3 * N // 4) or tuple(eo.shape) != (M, N // 32):
+        raise RuntimeError(f"yume_amd.gemm_f6_mxout: out {tuple(out.shape)}, eo {tuple(eo.shape)} do not fit M={M}, N={N}")
+    (ap, lda), (eap, ldea), (wp, ldw), (ewp, ldew) = _rows(a6, "a6"), _rows(ea, "ea"), _rows(w6, "w6"), _rows(ew, "ew")
+    (op, ldo), (eop, ldeo) = _rows(out, "out"), _rows(eo, "eo")
+    rc = lib.yume_gemm_f6_mxout(ap, lda, eap, ldea, wp, ldw, ewp, ldew, _ptr(bias), M, N, K, epi, op, ldo, eop, ldeo, _stream())
+    _lib.check(rc, "yume_gemm_f6_mxout")
+    return out, eo
+
+
+def gemm_f6_mx(a6, ea, w6, ew, bias, out, epi=EPI_F32, gate=None, gate_stride=0, row_idx=None):
+    """the MX6 consumer: acc = sum over 32-k blocks of 2^(ea[m, b] - 127) 2^(ew[n, b] - 127) * (a6 @ w6.T restricted to the block);
+    y = acc + bias; epilogue F32 or RESID (yume_hip.h)."""
+    lib = _lib.load()
+    M, N, K = _f6_operands("gemm_f6_mx", a6, ea, w6, ew)
+    (ap, lda), (eap, ldea), (wp, ldw), (ewp, ldew) = _rows(a6, "a6"), _rows(ea, "ea"), _rows(w6, "w6"), _rows(ew, "ew")
+    op, ldo = _rows(out, "out")
+    rc = lib.yume_gemm_f6_mx(ap, lda, eap, ldea, wp, ldw, ewp, ldew, _ptr(bias), M, N, K, epi, op, ldo, _ptr(gate), gate_stride,
+                             _ptr(row_idx), _stream())
+    _lib.check(rc, "yume_gemm_f6_mx")
+    return out
+
+
 # Scratch buffers of the split-K GEMM and the attention key-range split are keyed by (device, stream): two callers on
 # different HIP streams of one device (a VAE decode overlapped with the next chunk's denoise, say) never share partials.
 _splitk_ws = {}
