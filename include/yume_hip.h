@@ -505,6 +505,13 @@ int yume_transpose_bf16(const void* in, int in_bf16, int64_t ldi, int64_t rows, 
  *   levels on csrc/conv_halo_n.hpp (r6; YUME_CONV_HALO_N=0); the encoders' first convolution (8 -> 96, 16 -> 160 channels) on csrc/conv_in.hpp
  *   (r6: weights resident in registers; YUME_CONV_IN=0); everything else on the GEMM kernels with a
  *   gathering A loader. YUME_CONV_KORDER=0/1/2 selects the K walk of that loader (default 2: dt, channel tile, dh, dw).
+ * One-frame forms (r24; no signature changed, ABI 9): a causal 3x3x3 convolution of ONE frame without a cache reads zeros through its taps
+ *   dt = 0, 1, so the call kt = 1, pt = 0 with W pointing at element 18*Cin of every 27-tap row (ldw unchanged: ldw is the ROW STRIDE of W,
+ *   and only >= the padded K of the call made) computes the same sum. Every kernel above takes that form: the halo-tile kernel and the
+ *   encoders' first-convolution kernel through an instance of their own (`conv_halo16_kernel<0, 1>`, `conv_in_kernel<.., KT = 1>`: nine
+ *   taps resident in registers instead of 27; YUME_CONV_LOG=1 prints `halo` / `conv_in` with k=1x3x3), under the same shape rules as
+ *   their 3x3x3 instances. The call reads W up to K = kh*kw*Cin rounded up to 64 in every row: at Cin = 8 / 16 that leaves a 27-tap row
+ *   behind its slice, so there the caller passes a zero-padded copy of the slice (yume_amd.vae.live_view_fits).
  * epi: YUME_EPI_BF16 (bias), YUME_EPI_F32, YUME_CONV_EPI_ADD (out = acc + bias + add[m, co], add bf16 [M, ldadd] —
  *      the ResidualBlock skip, vae2_2.py:239), YUME_CONV_EPI_TSPLIT (upsample3d time_conv, vae2_2.py:145-153:
  *      channel halves of frame t become frames 2t and 2t+1: out[((2t+j)*Ho*Wo + hw), c] for co = j*Cout/2 + c),

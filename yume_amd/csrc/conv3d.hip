@@ -264,7 +264,7 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
         if (log_on) fprintf(stderr, "[conv3d_cl] conv_in M=%lld Cin=%lld Cout=%lld k=%dx%dx%d\n", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw);
         int rc = 0;
         if (Cin == 8) {
-            rc = conv_in::launch<8, 6>(ip, To, Ho, Wo, s);
+            rc = kt == 1 ? conv_in::launch<8, 6, 1>(ip, To, Ho, Wo, s) : conv_in::launch<8, 6>(ip, To, Ho, Wo, s);
         } else {
             for (int ch = 0; ch < 2 && rc == 0; ++ch) {          // 160 output channels = two launches of 80 (280 weight registers per lane each)
                 conv_in::Params q = ip;
@@ -272,7 +272,7 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
                 q.bias = bias ? bias + ch * 80 : nullptr;
                 q.out = ip.out + ch * 80;
                 q.cout = 80;
-                rc = conv_in::launch<16, 5>(q, To, Ho, Wo, s);
+                rc = kt == 1 ? conv_in::launch<16, 5, 1>(q, To, Ho, Wo, s) : conv_in::launch<16, 5>(q, To, Ho, Wo, s);
             }
         }
         YUME_REQUIRE(rc == 0, "conv3d_cl: too many tiles");
@@ -291,7 +291,10 @@ extern "C" int yume_conv3d_cl(const void* x, const void* cache, int64_t ldc, int
         YUME_REQUIRE(nt < (1ll << 31), "conv3d_cl: too many tiles");
         static const bool log_on = [] { const char* v = getenv("YUME_CONV_LOG"); return v && atoi(v) != 0; }();
         if (log_on) fprintf(stderr, "[conv3d_cl] halo M=%lld Cin=%lld Cout=%lld k=%dx%dx%d\n", (long long)M, (long long)Cin, (long long)Cout, kt, kh, kw);
-        hipLaunchKernelGGL(conv_halo::conv_halo16_kernel<0>, dim3((unsigned)nt), dim3(256), 0, s, hp);
+        if (kt == 1)
+            hipLaunchKernelGGL((conv_halo::conv_halo16_kernel<0, 1>), dim3((unsigned)nt), dim3(256), 0, s, hp);
+        else
+            hipLaunchKernelGGL(conv_halo::conv_halo16_kernel<0>, dim3((unsigned)nt), dim3(256), 0, s, hp);
         YUME_CHECK_LAUNCH("conv3d_cl");
         return YUME_OK;
     }

@@ -51,7 +51,9 @@ __device__ __forceinline__ i32x4 frame_srd(const Params& p, int ti) {
     return d;
 }
 
-template <int UNUSED = 0>
+// KT = 3: the causal 3x3x3 (frames to - 2 .. to); KT = 1: its one-frame (1,3,3) form with pt = 0 (r24: a first-chunk pass has no frames
+// to - 2, to - 1; `w` is then the nine-tap K range of dt = 2, a view into the 27-tap rows with their ldw)
+template <int UNUSED = 0, int KT = 3>
 __global__ __launch_bounds__(256, 1) void conv_halo16_kernel(Params p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * HALO_BYTES];
     const int tid = threadIdx.x;
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo16_kernel(Params p) {
     //      (rows n >= cout do not exist in the weight: their lanes read row cout - 1 and are zeroed)
     const unsigned short* wrow = p.w + (int64_t)min(l15, p.cout - 1) * p.ldw + l4 * 8;
     const bool wreal = l15 < p.cout;
-    const int nc = p.C / 64, nstep = 3 * nc;
+    const int nc = p.C / 64, nstep = KT * nc;
     auto load_b = [&](bf16x8_t (&b)[9][2], int step) {
         const int dt = step / nc, c0 = (step - dt * nc) * 64;
 #pragma unroll
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo16_kernel(Params p) {
     for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     bf16x8_t bcur[9][2], bnext[9][2];
-    stage(0, frame_srd(p, to - 2), 0u);
+    stage(0, frame_srd(p, to - (KT - 1)), 0u);
     load_b(bcur, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo16_kernel(Params p) {
         const int buf = step & 1;
         if (step + 1 < nstep) {                                          // (uniform) next halo into the other buffer, next weights into registers
             const int dtn = (step + 1) / nc, cn = (step + 1) - dtn * nc;
-            stage(buf ^ 1, frame_srd(p, to - 2 + dtn), (unsigned)cn * 128u);
+            stage(buf ^ 1, frame_srd(p, to - (KT - 1) + dtn), (unsigned)cn * 128u);
             load_b(bnext, step + 1);
         }
         const char* hb = smem + buf * HALO_BYTES;
@@ -178,7 +180,8 @@ inline bool applies(int64_t Cin, int64_t Cout, int kt, int kh, int kw, int st, i
                     int64_t Ho, int64_t Wo, int64_t ldc, int64_t ldo, int64_t ldw, int epi) {
     static const bool on = [] { const char* v = getenv("YUME_CONV_HALO"); return !v || atoi(v) != 0; }();
     if (!on || epi != YUME_EPI_BF16 || ups || st != 1 || sh != 1 || sw != 1) return false;
-    if (kt != 3 || kh != 3 || kw != 3 || pt != 2 || ph != 1 || pw != 1 || Cout > 16 || (Cin % 64) != 0) return false;
+    if (kh != 3 || kw != 3 || ph != 1 || pw != 1 || Cout > 16 || (Cin % 64) != 0) return false;
+    if (!((kt == 3 && pt == 2) || (kt == 1 && pt == 0))) return false;           // the causal 3x3x3, or its one-frame form (KT = 1)
     if (Ho != Hin || Wo != Win || (ldo != 8 && ldo != 16) || ldo < Cout || (Cout % 4) != 0 || (ldc % 8) != 0 || (ldw % 8) != 0) return false;
     if (Hin * Win * ldc * 2 >= 0x7fffff00ll) return false;
     return Ho * Wo >= 64 * 1024;           // the full-resolution head; small frames stay on the GEMM kernels

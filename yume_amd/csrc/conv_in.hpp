@@ -17,7 +17,9 @@
 //     zero too, but 0 x NaN-bits would poison the sum);
 //   * operand order as conv_halo_n: weights first, so a lane holds 4 consecutive channels of one position: 8-byte bf16 stores.
 // The work is 42 (2 x 70) MFMAs per 16 positions: the kernel is bound by its output stream. Compiler-scheduled; nothing names registers.
-// Roofline: HBM (2 * positions * Cout bytes written); MFMA work 2 * positions * Cout * 27 * Cin flop.
+// KT = 1 (r24): the one-frame form of the same layer — kt = 1, pt = 0, `w` = the nine taps of dt = 2 (VaeEngine.live_taps: the first pass of an
+// encode has no frames -2, -1). One frame of halo, 3 (5) k-steps, 72 (100) weight registers; everything else is the code above.
+// Roofline: HBM (2 * positions * Cout bytes written); MFMA work 2 * positions * Cout * 9 KT * Cin flop.
 #pragma once
 #include "gemm_core.hpp"
 
@@ -35,19 +37,20 @@ struct Params {
     int tiles_w, tiles_h;
 };
 
-template <int CIN, int NJ, int TH, int TW>
+template <int CIN, int NJ, int TH, int TW, int KT = 3>
 __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
-    constexpr int NKS = (27 * CIN + 31) / 32;            // 7 / 14 k-steps
+    constexpr int NTAP = 9 * KT;                         // KT = 3: the causal 3x3x3; KT = 1: the one-frame (1,3,3) form, pt = 0 (r24)
+    constexpr int NKS = (NTAP * CIN + 31) / 32;          // 7 / 14 k-steps (KT = 1: 3 / 5)
     constexpr int REC = CIN * 2;                         // bytes per position
     constexpr int HH = TH + 2, HW = TW + 2;
     constexpr int FRAME = HH * HW * REC;
-    constexpr int ZERO = 3 * FRAME;                      // a zero record behind the three frames
+    constexpr int ZERO = KT * FRAME;                     // a zero record behind the KT frames
     constexpr int MT = TH * TW / 16;                     // m-tiles of 16 consecutive columns
     constexpr int MPW = MT / 4;                          // per wave
     constexpr int MI = 2;
     static_assert(TW % 16 == 0 && MT % 4 == 0 && MPW % MI == 0, "tile shape");
     static_assert(CIN == 8 || CIN == 16, "8 or 16 input channels");
-    __shared__ __attribute__((aligned(16))) char halo[3 * FRAME + 64];
+    __shared__ __attribute__((aligned(16))) char halo[KT * FRAME + 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kb = lane >> 4;
 
     // ---- weights and bias into registers (once per launch) ----
@@ -58,7 +61,9 @@ __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (n < p.cout) v = *reinterpret_cast<const u32x4*>(p.w + (int64_t)n * p.ldw + 32 * ks + 8 * kb);
+            // (KT = 1: the columns behind the nine taps are another tap's weights when `w` is a view into a 27-tap row)
+            const bool live = KT == 3 || (CIN == 8 ? 4 * ks + kb : 2 * ks + (kb >> 1)) < NTAP;
+            if (n < p.cout && live) v = *reinterpret_cast<const u32x4*>(p.w + (int64_t)n * p.ldw + 32 * ks + 8 * kb);
             wf[j][ks] = __builtin_bit_cast(bf16x8_t, v);
         }
     }
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
     for (int ks = 0; ks < NKS; ++ks) {
         const int tap = CIN == 8 ? 4 * ks + kb : 2 * ks + (kb >> 1);
         const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
-        toff[ks] = tap < 27 ? dt * FRAME + (dh * HW + dw) * REC + (CIN == 16 ? (kb & 1) * 16 : 0) : -1;
+        toff[ks] = tap < NTAP ? dt * FRAME + (dh * HW + dw) * REC + (CIN == 16 ? (kb & 1) * 16 : 0) : -1;
     }
     if (tid < 4) reinterpret_cast<u32x4*>(halo + ZERO)[tid] = u32x4{0u, 0u, 0u, 0u};
 
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
     const int per = gridDim.x >> 3;
     // A tile's halo (frames to-2 .. to, rows h0-1 .. h0+TH, columns w0-1 .. w0+TW) travels global -> registers -> LDS: the loads of tile k + 1
     // are issued before tile k is computed and stored into the (single) LDS image behind it, so their latency hides under the MFMAs.
-    constexpr int NREC = (3 * HH * HW + 255) / 256;
+    constexpr int NREC = (KT * HH * HW + 255) / 256;
     u32x4 hv0[NREC], hv1[CIN == 16 ? NREC : 1];
     auto tile_origin3 = [&](int k, int& to, int& h0, int& w0) {
         const int t = start + k;
@@ -100,8 +105,8 @@ __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
         for (int u = 0; u < NREC; ++u) {
             const int r = tid + 256 * u;
             const int f = r / (HH * HW), q = r - f * (HH * HW), hr = q / HW, wc = q - hr * HW;
-            const int ti = to + f - 2, hi = h0 + hr - 1, wi = w0 + wc - 1;
-            const bool inside = r < 3 * HH * HW && hi >= 0 && hi < p.H && wi >= 0 && wi < p.W && (ti >= 0 ? ti < p.Tin : p.cache != nullptr);
+            const int ti = to + f - (KT - 1), hi = h0 + hr - 1, wi = w0 + wc - 1;
+            const bool inside = r < KT * HH * HW && hi >= 0 && hi < p.H && wi >= 0 && wi < p.W && (ti >= 0 ? ti < p.Tin : p.cache != nullptr);
             const unsigned short* src = (ti >= 0 ? p.x + (int64_t)ti * p.H * p.W * CIN : p.cache + (int64_t)(ti + 2) * p.H * p.W * CIN) +
                                         ((int64_t)hi * p.W + wi) * CIN;
             hv0[u] = u32x4{0u, 0u, 0u, 0u};
@@ -116,7 +121,7 @@ __global__ __launch_bounds__(256, 1) void conv_in_kernel(Params p) {
 #pragma unroll
         for (int u = 0; u < NREC; ++u) {
             const int r = tid + 256 * u;
-            if (r < 3 * HH * HW) {
+            if (r < KT * HH * HW) {
                 *reinterpret_cast<u32x4*>(halo + r * REC) = hv0[u];
                 if (CIN == 16) *reinterpret_cast<u32x4*>(halo + r * REC + 16) = hv1[u];
             }
@@ -179,14 +184,15 @@ inline bool applies(int64_t Cin, int64_t Cout, int kt, int kh, int kw, int st, i
                     int64_t Ho, int64_t Wo, int64_t ldc, int64_t ldo, int64_t ldw, int epi) {
     static const bool on = [] { const char* v = getenv("YUME_CONV_IN"); return !v || atoi(v) != 0; }();
     if (!on || ups || epi != YUME_EPI_BF16) return false;
-    if (kt != 3 || kh != 3 || kw != 3 || st != 1 || sh != 1 || sw != 1 || pt != 2 || ph != 1 || pw != 1) return false;
+    if (kh != 3 || kw != 3 || st != 1 || sh != 1 || sw != 1 || ph != 1 || pw != 1) return false;
+    if (!((kt == 3 && pt == 2) || (kt == 1 && pt == 0))) return false;           // the causal 3x3x3, or its one-frame form (KT = 1)
     if (!((Cin == 8 && Cout == 96) || (Cin == 16 && Cout == 160)) || ldc != Cin) return false;
-    if (Ho != Hin || Wo != Win || (ldo % 4) != 0 || ldo < Cout || (ldw % 8) != 0 || ldw < 32 * ((27 * Cin + 31) / 32)) return false;
+    if (Ho != Hin || Wo != Win || (ldo % 4) != 0 || ldo < Cout || (ldw % 8) != 0 || ldw < 32 * ((9 * kt * Cin + 31) / 32)) return false;
     if (Hin * Win * Cin * 2 >= 0x7fffff00ll) return false;
     return Ho * Wo >= 16 * 1024;
 }
 
-template <int CIN, int NJ>
+template <int CIN, int NJ, int KT = 3>
 inline int launch(Params hp, int64_t To, int64_t Ho, int64_t Wo, hipStream_t s) {
     constexpr int TH = 8, TW = 64;
     hp.tiles_w = (int)((Wo + TW - 1) / TW);
@@ -199,7 +205,7 @@ inline int launch(Params hp, int64_t To, int64_t Ho, int64_t Wo, hipStream_t s) 
         return n > 0 ? n : 256;
     }();
     const int64_t per_xcd = (nt + 7) / 8 < (ncu + 7) / 8 ? (nt + 7) / 8 : (ncu + 7) / 8;
-    hipLaunchKernelGGL((conv_in_kernel<CIN, NJ, TH, TW>), dim3((unsigned)(8 * per_xcd)), dim3(256), 0, s, hp);
+    hipLaunchKernelGGL((conv_in_kernel<CIN, NJ, TH, TW, KT>), dim3((unsigned)(8 * per_xcd)), dim3(256), 0, s, hp);
     return 0;
 }
 

@@ -50,6 +50,27 @@ def upfold_qualifies(cin, cout):
     return cin % 64 == 0 and cout >= 192
 
 
+def live_tap_form(k, pad_t, T, has_cache, stride=(1, 1, 1)):
+    """(k, pad_t, first_tap) a temporal convolution runs as under the engine's live_taps option. The only place the rule lives. A causal
+    convolution with kt == 3, pt == 2 and stride 1 over ONE frame that has no cache entry yet reads the frames -2, -1, 0 for its only
+    output frame; -2 and -1 are zeros, so the sum over dt = kt - 1 alone is the same number in real arithmetic: the call runs as the
+    (1, kh, kw) convolution with pt = 0 on the K range of temporal tap first_tap = kt - 1. Everything else keeps today's call
+    (first_tap = 0). The rule looks at the call's own frame count and cache, never at H, W, `group` or the length of the video."""
+    kt, kh, kw = k
+    if kt == 3 and pad_t == 2 and tuple(stride) == (1, 1, 1) and T == 1 and not has_cache:
+        return (1, kh, kw), 0, kt - 1
+    return (kt, kh, kw), pad_t, 0
+
+
+def live_view_fits(k, cip):
+    """May the live K range of a packed weight row be handed to the kernels as a VIEW (row stride unchanged)? A packed row holds
+    K = kt kh kw cip elements ordered (dt, dh, dw, ci), zero padded to 64; the live slice starts at (kt - 1) kh kw cip and the
+    dispatcher reads it up to its own padding to 64: legal only while that stays inside the row (the last row ends the buffer).
+    True for cip = 32, 48, 64, 96, 128, 160, ...; False for cip = 8 and 16 (3x3x3), where _pack keeps a zero-padded copy instead."""
+    kt, kh, kw = k
+    return (kt - 1) * kh * kw * cip + _ru(kh * kw * cip, 64) <= _ru(kt * kh * kw * cip, 64)
+
+
 _FOLD_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # S(e, t): the 3x3 taps that phase parity e reads at 2x2 tap t
 
 
@@ -112,6 +133,12 @@ class VaeEngine:
         # to bf16 at pack time, fold_upsample_weight): 4 taps instead of 9. Not bit-equal to the 9-tap path (the summed weights are rounded
         # once more, 1.6-1.8e-3 rel-L2 per convolution). Independent of fp8_conv. Part of the pack key: toggling it repacks.
         self.fold_upsample = os.environ.get("YUME_VAE_UPFOLD", "0") == "1"
+        # r24 (env YUME_VAE_LIVE_TAPS=1, off by default): the first pass of every encode / decode (one frame, an empty cache) runs its
+        # 3x3x3 convolutions on the nine taps of dt = 2 alone — the 18 taps of the frames -2, -1 multiply zeros (live_tap_form). The same
+        # value in real arithmetic; the fp32 sum can differ in its last bits where a K tile straddles taps. The weights are a view into
+        # the packed rows, or a zero-padded copy packed beside them where the view would read past the row (live_view_fits: the
+        # encoders' first convolution). Independent of fp8_conv and fold_upsample. Part of the pack key (the copies).
+        self.live_taps = os.environ.get("YUME_VAE_LIVE_TAPS", "0") == "1"
 
     # ------------------------------------------------------------------ weights
     def _pack(self):
@@ -139,6 +166,12 @@ class VaeEngine:
                 b = torch.zeros(cop, dtype=torch.float32, device=dev)
                 b[:co] = sd[name + ".bias"].float()
                 P[name] = dict(w=full.to(torch.bfloat16).contiguous(), b=b, co=co, cop=cop, ci=ci, cip=cip, k=(kt, kh, kw))
+                if self.live_taps and kt == 3 and not live_view_fits((kt, kh, kw), cip):
+                    # the K range of dt = kt - 1 as rows of its own, zero padded to 64: a view would be read past the end of the row
+                    Kl = kh * kw * cip
+                    wl = torch.zeros(cop, _ru(Kl, 64), dtype=torch.bfloat16, device=dev)
+                    wl[:, :Kl] = P[name]["w"][:, (kt - 1) * Kl:kt * Kl]
+                    P[name]["wl"] = wl
                 if self.fp8_conv and name.endswith((".residual.2", ".residual.6")) and ci % 128 == 0 and (kt, kh, kw) == (3, 3, 3):
                     # e4m3 bytes [cop, 27 ci] of the bf16 weights with one fp32 scale per output channel (amax / 448, 1 for a zero row)
                     wq = torch.empty((cop, K), dtype=torch.uint8, device=dev)
@@ -158,7 +191,7 @@ class VaeEngine:
         self.zero = torch.zeros(64, dtype=torch.bfloat16, device=dev)
 
     def ensure_packed(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.module.parameters()) + (bool(self.fp8_conv), bool(self.fold_upsample))
+        key = tuple((p.data_ptr(), p._version) for p in self.module.parameters()) + (bool(self.fp8_conv), bool(self.fold_upsample), bool(self.live_taps))
         if key != self._key:
             self._pack()
             self._key = key
@@ -199,7 +232,13 @@ class VaeEngine:
             epi, operand = V.EPI_RMS_SILU, self.P[norm + ".gamma"]
         else:
             epi, operand = (V.EPI_ADD if add is not None else V.EPI_BF16), add
-        V.conv3d_cl(x, cache.get(name), p["w"], p["b"], p["cop"], (kt, kh, kw), (1, 1, 1), (kt - 1, kh // 2, kw // 2), False,
+        w, k, pt = p["w"], (kt, kh, kw), kt - 1
+        if self.live_taps:
+            k, pt, dt0 = live_tap_form(p["k"], kt - 1, T, cache.get(name) is not None)
+            if dt0:
+                # the K range of the live temporal tap: a view with the row stride of the packed rows, or the copy _pack kept
+                w = p["wl"] if "wl" in p else p["w"][:, dt0 * kh * kw * p["cip"]:]
+        V.conv3d_cl(x, cache.get(name), w, p["b"], p["cop"], k, (1, 1, 1), (pt, kh // 2, kw // 2), False,
                     out, epi, add=operand, zero_page=self.zero)
         self._update_cache(cache, name, x)
         return out
@@ -236,7 +275,12 @@ class VaeEngine:
         if out.shape[3] != p["cop"]:
             out.zero_()
         cq, ce = cache.get(name + "#q"), cache.get(name + "#e")
-        V.conv3d_cl_f8mx(q, e, None if cq is None else (cq, ce), p["wq"], p["sw"], p["b"], p["cop"], p["k"], out,
+        wq, k = p["wq"], p["k"]
+        if self.live_taps:
+            k, _, dt0 = live_tap_form(p["k"], p["k"][0] - 1, T, cq is not None)
+            if dt0:
+                wq = p["wq"][:, dt0 * k[1] * k[2] * C:]      # e4m3 rows hold exactly K bytes: the live range ends the row, sw unchanged
+        V.conv3d_cl_f8mx(q, e, None if cq is None else (cq, ce), wq, p["sw"], p["b"], p["cop"], k, out,
                          V.EPI_ADD if add is not None else V.EPI_BF16, add=add, zero_page=self.zero)
         self._update_cache(cache, name + "#q", q)
         self._update_cache(cache, name + "#e", e)

@@ -39,7 +39,7 @@ def conv3d_cl(x, cache, w, bias, cout, k, stride, pad, ups, out, epi=EPI_BF16, a
         _cl(add, "add")
         ldadd = add.shape[3]
     rc = lib.yume_conv3d_cl(x.data_ptr(), _ptr(cache), C, Tin, Hin, Win, cin if cin is not None else C, w.data_ptr(),
-                            w.shape[1], _ptr(bias), cout, k[0], k[1], k[2], stride[0], stride[1], stride[2], pad[0],
+                            w.stride(0), _ptr(bias), cout, k[0], k[1], k[2], stride[0], stride[1], stride[2], pad[0],
                             pad[1], pad[2], 1 if ups else 0, To, Ho, Wo, epi, out.data_ptr(), Cl,
                             _ptr(add), ldadd, zero_page.data_ptr(), _stream())
     _lib.check(rc, "yume_conv3d_cl")
