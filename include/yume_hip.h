@@ -246,6 +246,44 @@ int yume_gemm_f6_mxout(const void* A6, int64_t lda, const void* ea, int64_t ldea
                        const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo,
                        void* eo, int64_t ldeo, void* stream);
 
+/* ---- INT8 QKV / cross-q projections (r25; functions added, no argument list changed: ABI 9) -------------------------------
+ * replaces (opt-in, DiTEngine.int8_qkv): the first adaLN + QKV projection and norm3 + cross-attention q projection of a block.
+ *
+ * The format, once (yume_amd/csrc/i8.hpp): symmetric int8 with one fp32 scale per row.
+ *     amax = max_k |x[r, k]| over the row's bf16 values;  scale[r] = amax / 127.0f (one IEEE fp32 division; 1.0f for an all-zero row);
+ *     q[r, k] = rne(clamp(x[r, k] / scale[r], +-127))               (clamped BEFORE the rounding: no byte is 0x80)
+ * x / scale is formed with a reciprocal, as yume_quant_rows_e4m3 forms it: |q - x / scale| <= 0.5 + 2^-20 |x / scale|.
+ * Non-finite input: a row that holds an Inf or a NaN gets scale = NaN and all bytes 0 (its GEMM outputs are then NaN); other rows are
+ * not affected.
+ *
+ * yume_quant_rows_i8: the stand-alone quantiser, x bf16 [R, K] (row stride ldx elements), q i8 [R, K] (row stride ldq bytes), scale fp32
+ *   [R]. Checks and untouched bytes as yume_quant_rows_e4m3: K % 16 == 0, ldq % 16 == 0, ldx % 8 == 0, ldx >= K, ldq >= K, x and q 16-byte
+ *   aligned; bytes beyond K of a q row and rows beyond R are not written; R == 0: YUME_OK, nothing is launched.
+ *   YUME_NORM_LOG=1: `[quant] rows_i8 ...` per launch.
+ * yume_adaln_modulate_i8: yume_adaln_modulate(..., out_kind = 0) followed by yume_quant_rows_i8 on its bf16 output, in one kernel and
+ *   without the bf16 row; q and scale equal the two-call composite bit for bit. Argument list, checks and untouched bytes are those of
+ *   yume_adaln_modulate_e4m3. YUME_NORM_LOG=1: `[norm] adaln_i8<MAXV> ...` / `[norm] adaln2_i8 ...`.
+ * yume_gemm_i8:   acc[m, n] = sum_k Aq[m, k] * Wq[n, k]  (signed bytes, int32 sum, EXACT: v_mfma_i32_16x16x64_i8);
+ *   y = float(acc) * sa[m] * sw[n] + bias[n] (float(): round to nearest even, exact below 2^24);  then `epi`: YUME_EPI_BF16 or
+ *   YUME_EPI_F32 into out (row stride ldo elements); any other epilogue: YUME_EUNSUP. Every byte value is taken, 0x80 = -128 included.
+ *   Aq i8 [M, K] (row stride lda bytes), Wq i8 [N, K] (ldw), sa fp32 [M], sw fp32 [N], bias fp32 [N] or NULL.
+ *   Checks (YUME_EINVAL): those of yume_gemm_f8 — K % 128 == 0, lda % 16 == 0, ldw % 16 == 0, N % 4 == 0, ldo % 4 == 0, Aq / Wq / out /
+ *   sw / bias 16-byte aligned — and K <= 131072 (127 * 128 * K stays below 2^31). One 256 x 256 output tile per workgroup, nothing is
+ *   handed between workgroups; no workspace, no allocation, the caller's stream.
+ * yume_gemm_i8_splitt (the QKV form): the same sum and scales, stored as yume_gemm_f8_splitt stores them: columns n < n_split to
+ *   out[m, n] (bf16 row-major), columns n >= n_split to outT[n - n_split, m] (bf16, K-major); the checks of yume_gemm_f8_splitt
+ *   (n_split % 256 == 0, ...) and K <= 131072.
+ * YUME_GEMM_LOG=1: `[gemm_i8] i8 M= N= K= epi= ...` per launch (`... ldt= n_split=` for the QKV form, epi = 4). */
+int yume_quant_rows_i8(const void* x, int64_t ldx, int64_t R, int64_t K, void* q, int64_t ldq, float* scale, void* stream);
+int yume_adaln_modulate_i8(const float* x, int64_t ldx, int64_t T, int64_t C, float eps, const float* mul,
+                           const float* add, int64_t tab_stride, const int32_t* row_idx, int add_one,
+                           void* q, int64_t ldq, float* scale, void* stream);
+int yume_gemm_i8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
+                 const float* bias, int64_t M, int64_t N, int64_t K, int epi, void* out, int64_t ldo, void* stream);
+int yume_gemm_i8_splitt(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw,
+                        const float* bias, int64_t M, int64_t N, int64_t K,
+                        void* out, int64_t ldo, void* outT, int64_t ldt, int64_t n_split, void* stream);
+
 /* ---- RMSNorm over the hidden dim (+ optional 3D RoPE), in place, bf16 -----------------------
  * replaces: wan23/modules/model.py:121-137 (WanRMSNorm on q,k over the FULL hidden dim C),
  *           :38-118 (rope_apply: interleaved-pair complex multiply with the per-token table).

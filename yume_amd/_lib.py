@@ -34,6 +34,10 @@ SIGNATURES = {
     "yume_adaln_modulate_mx_e2m3": [_P, _L, _L, _L, _F, _P, _P, _L, _P, _I, _P, _L, _P, _L, _P],
     "yume_gemm_f6_mx": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P, _P],
     "yume_gemm_f6_mxout": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _L, _P],
+    "yume_quant_rows_i8": [_P, _L, _L, _L, _P, _L, _P, _P],
+    "yume_adaln_modulate_i8": [_P, _L, _L, _L, _F, _P, _P, _L, _P, _I, _P, _L, _P, _P],
+    "yume_gemm_i8": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _I, _P, _L, _P],
+    "yume_gemm_i8_splitt": [_P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _L, _L, _P],
     "yume_rmsnorm_f32": [_P, _L, _L, _L, _F, _P, _P, _L, _P],
     "yume_gemm_bf16_batched": [_P, _L, _L, _P, _L, _L, _L, _L, _L, _I, _P, _L, _L, _L, _I, _P],
     "yume_gemm_splitk_workspace_bytes": [_L, _L, _I],

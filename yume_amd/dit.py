@@ -111,6 +111,14 @@ class DiTEngine:
         # pack key: flipping it re-packs.
         self.fp6_ffn = os.environ.get("YUME_FP6_FFN", "0") == "1"
         self._fp6_ffn_said = False
+        # r25: the projections of fp8_qkv in symmetric int8 instead, one fp32 scale per token row and per output channel (csrc/i8.hpp): seven
+        # bits under the row's largest value where e4m3 carries three mantissa bits, at the same MFMA rate on the same bytes.
+        # adaln_modulate_i8 -> gemm_i8_splitt and adaln_modulate_i8 (norm3) -> gemm_i8 (_qkv_step, _cross_q_step); the weights are quantised
+        # once at pack time (ops.quant_rows_i8), the bf16 weights stay. Wins over fp8_qkv where both are on (said once under YUME_GEMM_LOG).
+        # Independent of the FFN and attention options. Off by default = today's path, bit for bit; env YUME_INT8_QKV=1 turns it on. Part of
+        # the pack key: flipping it re-packs.
+        self.int8_qkv = os.environ.get("YUME_INT8_QKV", "0") == "1"
+        self._int8_qkv_said = False
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -129,7 +137,7 @@ class DiTEngine:
     def _param_key(self):
         # walked once per forward: (storage address, in-place version, dtype) of every parameter — a load_state_dict, an
         # optimizer step or a .to(dtype) re-packs; cheap next to one forward (≈1 k tensors), and cached per forward call
-        return (self.q_prescale, bool(self.fp8_ffn), bool(self.fp8_qkv), bool(self.fp6_ffn)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
+        return (self.q_prescale, bool(self.fp8_ffn), bool(self.fp8_qkv), bool(self.fp6_ffn), bool(self.int8_qkv)) + tuple((p.data_ptr(), p._version, p.dtype) for p in self.model.parameters())
 
     def _pack(self):
         m = self.model
@@ -220,6 +228,17 @@ class DiTEngine:
                         sys.stderr.write("[fp8_qkv] the blocks have no norm3 weights: the cross-attention q projection stays bf16\n")
                 elif log and not blocks:
                     sys.stderr.write(f"[fp8_qkv] the blocks keep bf16 QKV / cross-q linears: dim={C} is not a multiple of 128\n")
+            if self.int8_qkv:
+                log = os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0")
+                if C % 128 == 0:       # (the condition of fp8_qkv: K % 128 == 0 and n_split = 2 C a multiple of 256)
+                    for wk, qk_, sk_ in (("wqkv", "wqkvi", "sqkvi"),) + ((("wq_c", "wq_ci", "sq_ci"),) if "n3w" in d else ()):
+                        d[qk_] = torch.empty(d[wk].shape, dtype=torch.int8, device=dev)
+                        d[sk_] = torch.empty(d[wk].shape[0], dtype=torch.float32, device=dev)
+                        ops.quant_rows_i8(d[wk], d[qk_], d[sk_])
+                    if "n3w" not in d and log and not blocks:
+                        sys.stderr.write("[int8_qkv] the blocks have no norm3 weights: the cross-attention q projection stays bf16\n")
+                elif log and not blocks:
+                    sys.stderr.write(f"[int8_qkv] the blocks keep bf16 QKV / cross-q linears: dim={C} is not a multiple of 128\n")
             blocks.append(d)
         P["blocks"] = blocks
         # cross-attention K / V projections of ALL blocks as one weight: the conditioning tokens are the same for every block,
@@ -477,8 +496,21 @@ class DiTEngine:
         """the first adaLN of a block and its QKV projection, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike: q | k into
         qk [n, 2C], V as the K-major image vt[:, :n]. With fp8_qkv (and a block packed for it) the adaLN kernel emits the e4m3 rows and their
         scales itself and the e4m3 GEMM writes both outputs (yume_gemm_f8_splitt); h is then not written. Row-local: the callers' row ranges
-        are handed on as they are. The byte and scale buffers are workspaces, allocated by the first eager forward."""
+        are handed on as they are. The byte and scale buffers are workspaces, allocated by the first eager forward. With int8_qkv the same pair
+        runs on int8 rows (yume_adaln_modulate_i8 -> yume_gemm_i8_splitt), in front of the e4m3 branch where both options are on."""
         T = self._timed
+        if "wqkvi" in d:
+            # (r25) int8 rows in front of the e4m3 branch: the adaLN kernel emits the int8 rows and their scales, the int8 GEMM writes both outputs
+            if self.fp8_qkv and not self._int8_qkv_said:
+                self._int8_qkv_said = True
+                if os.environ.get("YUME_GEMM_LOG", "0") not in ("", "0"):
+                    sys.stderr.write("[int8_qkv] fp8_qkv is on too: the qualifying blocks run the int8 QKV / cross-q projections\n")
+            n, C = h.shape
+            hq = self._buf("qkv_hi8", (n, C), torch.int8, grow_rows=True)
+            sh = self._buf("qkv_sh", (n,), torch.float32, grow_rows=True)
+            T("adaln", ops.adaln_modulate_i8, xs, scale_sa, shift_sa, ts, row_idx, True, hq, sh, eps)
+            T("gemm_qkv", ops.gemm_i8_splitt, hq, sh, d["wqkvi"], d["sqkvi"], d["bqkv"], qk, vt, 2 * C)
+            return
         if "wqkvq" not in d:
             T("adaln", ops.adaln_modulate, xs, scale_sa, shift_sa, ts, row_idx, True, h, 0, eps)
             T("gemm_qkv", ops.gemm_bf16, h, d["wqkv"], d["bqkv"], qk, EPI_BF16_SPLITT, out_t=vt, n_split=2 * self.model.dim, variant=self.gemm_variant)
@@ -491,9 +523,15 @@ class DiTEngine:
 
     def _cross_q_step(self, d, xs, h, q, eps):
         """norm3 (or, without its weights, the plain cast) of xs [n, C] and the cross-attention q projection into q [n, C], behind the same four
-        bodies. With fp8_qkv (and norm3 weights: an adaLN launch has to be there to emit the bytes) the pair runs in e4m3 as _qkv_step's."""
+        bodies. With fp8_qkv (and norm3 weights: an adaLN launch has to be there to emit the bytes) the pair runs in e4m3 as _qkv_step's; with int8_qkv, in int8 (yume_adaln_modulate_i8 -> yume_gemm_i8), in front of it."""
         T = self._timed
         n, C = h.shape
+        if "wq_ci" in d:
+            hq = self._buf("qkv_hi8", (n, C), torch.int8, grow_rows=True)
+            sh = self._buf("qkv_sh", (n,), torch.float32, grow_rows=True)
+            T("adaln", ops.adaln_modulate_i8, xs, d["n3w"], d["n3b"], 0, None, False, hq, sh, eps)
+            T("gemm_cross_q", ops.gemm_i8, hq, sh, d["wq_ci"], d["sq_ci"], d["bq_c"], q, EPI_BF16)
+            return
         if "wq_cq" not in d:
             if "n3w" in d:
                 T("adaln", ops.adaln_modulate, xs, d["n3w"], d["n3b"], 0, None, False, h, 0, eps)

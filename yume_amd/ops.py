@@ -250,6 +250,97 @@ def gemm_f8_splitt(aq, sa, wq, sw, bias, out, out_t, n_split):
     return out, out_t
 
 
+def _bytes(t, name):
+    """an int8 row tensor: torch.int8 or torch.uint8 (the kernels read signed bytes either way)"""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype not in (torch.int8, torch.uint8):
+        raise RuntimeError(f"yume_amd: {name} must be a device ('cuda') int8 / uint8 tensor")
+    return t
+
+
+def quant_rows_i8(x, q, scale):
+    """q i8 [R, K] = rne(clamp(x / scale[r], +-127)) with scale[r] = max|x[r]| / 127 (1 for a zero row; NaN and zero bytes for a row with a
+    non-finite value); x bf16 [R, K], scale fp32 [R] (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(x, "x", torch.bfloat16)
+    _bytes(q, "q")
+    _dev(scale, "scale", torch.float32)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    R, K = x.shape
+    if tuple(q.shape) != (R, K) or scale.dim() != 1 or scale.numel() != R or not scale.is_contiguous():
+        raise RuntimeError(f"yume_amd.quant_rows_i8: x {tuple(x.shape)}, q {tuple(q.shape)}, scale {tuple(scale.shape)} do not fit")
+    rc = lib.yume_quant_rows_i8(xp, ldx, R, K, qp, ldq, scale.data_ptr(), _stream())
+    _lib.check(rc, "yume_quant_rows_i8")
+    return q, scale
+
+
+def adaln_modulate_i8(x, mul, add, tab_stride, row_idx, add_one, q, scale, eps=1e-6):
+    """q i8 [T, C], scale fp32 [T] = quant_rows_i8(adaln_modulate(x, ..., out bf16)) in one kernel, bit for bit (yume_hip.h)."""
+    lib = _lib.load()
+    _dev(x, "x", torch.float32)
+    _bytes(q, "q")
+    _dev(scale, "scale", torch.float32)
+    xp, ldx = _rows(x, "x")
+    qp, ldq = _rows(q, "q")
+    T, C = x.shape
+    if tuple(q.shape) != (T, C) or scale.dim() != 1 or scale.numel() != T or not scale.is_contiguous():
+        raise RuntimeError(f"yume_amd.adaln_modulate_i8: x {tuple(x.shape)}, q {tuple(q.shape)}, scale {tuple(scale.shape)} do not fit")
+    rc = lib.yume_adaln_modulate_i8(xp, ldx, T, C, eps, mul.data_ptr(), add.data_ptr(), tab_stride, _ptr(row_idx),
+                                    1 if add_one else 0, qp, ldq, scale.data_ptr(), _stream())
+    _lib.check(rc, "yume_adaln_modulate_i8")
+    return q, scale
+
+
+def _i8_operands(what, aq, sa, wq, sw):
+    _bytes(aq, "aq")
+    _bytes(wq, "wq")
+    _dev(sa, "sa", torch.float32)
+    _dev(sw, "sw", torch.float32)
+    ap, lda = _rows(aq, "aq")
+    wp, ldw = _rows(wq, "wq")
+    M, K = aq.shape
+    N, K2 = wq.shape
+    if K != K2:
+        raise RuntimeError(f"yume_amd.{what}: K mismatch {K} vs {K2}")
+    if sa.dim() != 1 or sa.numel() != M or not sa.is_contiguous() or sw.dim() != 1 or sw.numel() != N or not sw.is_contiguous():
+        raise RuntimeError(f"yume_amd.{what}: scales sa {tuple(sa.shape)}, sw {tuple(sw.shape)} do not fit M={M}, N={N}")
+    return ap, lda, wp, ldw, M, N, K
+
+
+def gemm_i8(aq, sa, wq, sw, bias, out, epi=EPI_BF16):
+    """acc = aq @ wq.T (signed bytes: aq i8 [M,K], wq i8 [N,K]; int32, exact); y = float(acc) * sa[m] * sw[n] + bias; epilogue BF16 or F32."""
+    lib = _lib.load()
+    ap, lda, wp, ldw, M, N, K = _i8_operands("gemm_i8", aq, sa, wq, sw)
+    _dev(out, "out", torch.float32 if epi == EPI_F32 else torch.bfloat16)
+    op, ldo = _rows(out, "out")
+    if out.shape[0] < M or out.shape[1] < N:
+        raise RuntimeError(f"yume_amd.gemm_i8: out {tuple(out.shape)} does not hold [{M}, {N}]")
+    rc = lib.yume_gemm_i8(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, epi, op, ldo, _stream())
+    _lib.check(rc, "yume_gemm_i8")
+    return out
+
+
+def gemm_i8_splitt(aq, sa, wq, sw, bias, out, out_t, n_split):
+    """gemm_i8's sum and scales with the QKV epilogue of gemm_f8_splitt: columns n < n_split bf16 row-major into out [M, >= n_split], columns
+    n >= n_split as the K-major V^T image out_t[n - n_split, m] (bf16 [>= N - n_split, ldt >= M]); n_split % 256 == 0 (yume_hip.h)."""
+    lib = _lib.load()
+    ap, lda, wp, ldw, M, N, K = _i8_operands("gemm_i8_splitt", aq, sa, wq, sw)
+    op, ldo, tp, ldt = None, 0, None, 0
+    if out is not None:
+        _dev(out, "out", torch.bfloat16)
+        op, ldo = _rows(out, "out")
+        if out.shape[0] < M or out.shape[1] < n_split:
+            raise RuntimeError(f"yume_amd.gemm_i8_splitt: out {tuple(out.shape)} does not hold [{M}, {n_split}]")
+    if out_t is not None:
+        _dev(out_t, "out_t", torch.bfloat16)
+        tp, ldt = _rows(out_t, "out_t")
+        if out_t.shape[0] < N - n_split:
+            raise RuntimeError(f"yume_amd.gemm_i8_splitt: out_t {tuple(out_t.shape)} does not hold {N - n_split} rows")
+    rc = lib.yume_gemm_i8_splitt(ap, lda, sa.data_ptr(), wp, ldw, sw.data_ptr(), _ptr(bias), M, N, K, op, ldo, tp, ldt, n_split, _stream())
+    _lib.check(rc, "yume_gemm_i8_splitt")
+    return out, out_t
+
+
 EPI_MX_GELU = 7
 
 
