@@ -381,6 +381,29 @@ int yume_attn_fwd_ws(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
 int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
                      void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale,
                      int accumulate, int variant, void* workspace, int64_t workspace_bytes, float last_key_weight, void* stream);
+/* SLIDING-WINDOW / CAUSAL form (r26; a function added, no argument list changed: ABI 9). flash-attn 2.7 semantics, bottom-right aligned,
+ * with an explicit query position: row i of the call sits at pos(i) = q_pos0 + i on the key axis and
+ *   visible(i, j)  <=>  0 <= j < Lk  and  (win_left < 0 or j >= pos(i) - win_left)  and  (win_right < 0 or j <= pos(i) + win_right)
+ *   O[h,i,:] = sum_{visible j} e^{scale <Q_i,K_j>} V_j / sum_{visible j} e^{scale <Q_i,K_j>};   O[h,i,:] = 0 where row i sees no key (an
+ *   accumulate call then leaves the old O[h,i,:] as it is, bit for bit). Exact softmax over the visible set.
+ * replaces: wan23/modules/attention.py:24-130 flash_attention(causal=, window_size=) -> flash_attn_varlen_func(causal, window_size), reached
+ *           from WanSelfAttention.forward, wan23/modules/model.py:158-202 (WanModel(window_size=...)). causal is win_right = 0; flash-attn's
+ *           alignment of a call with Lq != Lk is q_pos0 = Lk - Lq; a caller that holds a row range of a longer sequence passes the first row's
+ *           own index. The reference's FA3 branch ignores the window; that is not reproduced.
+ * win_left / win_right: -1 = unbounded on that side. Checks (YUME_EINVAL by name `attn_fwd_band`): everything yume_attn_fwd_ws checks;
+ *    win_left, win_right >= -1; q_pos0 in [-2^31, 2^31).
+ * A (q_pos0, win_left, win_right) that hides no (i, j) pair of the call IS yume_attn_fwd_ws with the same arguments: same kernel choice, same
+ *    log line, same bits. Only a call that hides at least one pair runs the banded kernel (attn_band.hpp: attn_fwd_kernel_v2's tile walk over
+ *    the key tiles some row of a 128-query workgroup sees, the mask applied to the scores before the row maximum):
+ *    variant 0 and variant 11 = that kernel; any other variant: YUME_EUNSUP (the message names it).
+ * accumulate, ragged Lq, both scale modes and YUME_ATTN_KV_PADDED (accepted; it changes nothing here) as for yume_attn_fwd. No weighted last
+ *    key, no key-range split; the workspace is handed on to yume_attn_fwd_ws and otherwise unused.
+ * env YUME_ATTN_LOG=1: one line per banded call, `[attn_fwd_band] band q_pos0=.. left=.. right=.. tiles_min=.. tiles_max=.. Lq=.. Lk=.. H=..
+ *    ...` (the fewest and the most key tiles a workgroup walks). tests/test_attn_band_routes_gpu.py reads it back. */
+int yume_attn_fwd_band(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                       void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
+                       int64_t q_pos0, int64_t win_left, int64_t win_right,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 /* SEGMENTED form (r9): ONE launch serves nseg (1 .. 8) independent attention problems that share Q's and O's buffers and every shape but the
  * key count. Segment s owns the query rows [s * seg_pitch, s * seg_pitch + Lq_seg) of Q and O (seg_pitch >= Lq_seg, in rows; the rows of the
  * gap are neither read nor written) and attends over its own K[s] / Vt[s] (Lk[s] keys, key Lk[s] - 1 counting last_key_weight[s] times).

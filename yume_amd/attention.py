@@ -4,6 +4,10 @@ Same signature and return convention as the reference wrapper around flash-attn'
 [B, L, N, D] tensors of any float dtype on the GPU, output is [B, Lq, N, D] in q's dtype. Rebinding
 `wan23.modules.model.flash_attention = yume_amd.attention.flash_attention` in the reference tree is enough to
 route the reference model's attention through the gfx950 kernel.
+
+`causal` and `window_size` carry flash-attn 2.7's meaning (bottom-right aligned; yume_attn_fwd_band): per sample, query row i sits at
+(nk - nq) + i on the key axis and sees the keys within window_size[0] to its left and window_size[1] to its right (-1: unbounded; causal
+sets the right side to 0). A row that sees no key is 0. A window that hides nothing is the global call, bit for bit.
 """
 import math
 
@@ -18,9 +22,14 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
                     window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None):
     assert dtype in (torch.float16, torch.bfloat16)
     assert q.device.type == "cuda" and q.size(-1) <= 256
-    if causal or dropout_p != 0. or tuple(window_size) != (-1, -1):
-        raise NotImplementedError("yume_amd.flash_attention: only full (non-causal, no dropout, no window) attention "
-                                  "is used by the Yume models and implemented")
+    if dropout_p != 0.:
+        raise NotImplementedError("yume_amd.flash_attention: dropout is not implemented (no Yume model uses it)")
+    # flash-attn 2.7: causal is window_size[1] = 0; rows are bottom-right aligned, i.e. query row i of a sample sits at (nk - nq) + i
+    left, right = int(window_size[0]), int(window_size[1])
+    if left < -1 or right < -1:
+        raise ValueError(f"yume_amd.flash_attention: window_size={tuple(window_size)}: -1 (unbounded) or a non-negative width per side")
+    if causal:
+        right = 0
     if dtype != torch.bfloat16:
         raise NotImplementedError("yume_amd.flash_attention computes in bf16 (the reference default)")
     b, lq, n, d = q.shape
@@ -52,7 +61,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vi = vi.float()
         vt = torch.empty((n * d, (nk + 7) // 8 * 8), dtype=torch.bfloat16, device=q.device)
         ops.transpose_bf16(vi.contiguous(), vt)
-        ops.attn_fwd(qi, ki, vt, out[i, :nq], nq, nk, n, scale=scale)
+        ops.attn_fwd(qi, ki, vt, out[i, :nq], nq, nk, n, scale=scale, window=(left, right), q_pos0=nk - nq)
         if nq < lq:
             out[i, nq:].zero_()   # flash-attn's varlen packing leaves padded queries out; the reference never reads them
     return out.view(b, lq, n, d)[..., :d_in].type(out_dtype)

@@ -1,5 +1,5 @@
 // attn_fwd.hip — exact-softmax attention forward for head_dim 128, bf16 in / fp32 accumulate / bf16 out (gfx950): the C-ABI entry points
-// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_fwd_seg, yume_attn_fwd_batch, yume_attn_workspace_bytes,
+// (yume_attn_fwd, yume_attn_fwd_ws, yume_attn_fwd_kw, yume_attn_fwd_band, yume_attn_fwd_seg, yume_attn_fwd_batch, yume_attn_workspace_bytes,
 // yume_attn_batch_workspace_bytes) and the dispatcher behind them:
 // validate -> choose -> launch.
 //
@@ -15,6 +15,7 @@
 //   attn_short_kernel     attn_short.hpp      Lk <= 128: a head's K and V^T resident in one wave's registers (takes the weighted last key)
 // yume_attn_fwd_seg (several independent segments in one launch) has the segmented forms of the last two of its own: attn_seg.hpp.
 // yume_attn_fwd_batch (several stacked self-attention problems of one shape) has attn_fwd_kernel_v8's: attn_batch8.hip.
+// yume_attn_fwd_band (sliding-window / causal attention) has the banded form of attn_fwd_kernel_v2: attn_band.hpp, planned by attn_band_plan.hpp.
 // and attn_combine_kernel (attn_combine.hpp) merges the key-range pieces of a split v7 / v8 launch, planned by attn_plan.hpp.
 // The transposed formulation and the tile layouts the kernels share: attn_tile.hpp.
 #include "common.hpp"
@@ -28,6 +29,7 @@
 #include "attn_cross_rk.hpp"
 #include "attn_short.hpp"
 #include "attn_seg.hpp"
+#include "attn_band.hpp"
 #include <math.h>
 
 static_assert(attn_plan::QBLOCK == QB4 && attn_plan::KTILE == KT && attn_plan::HDIM == D, "attn_plan.hpp restates the tile constants");
@@ -262,6 +264,59 @@ extern "C" int yume_attn_fwd_kw(const void* Q, int64_t ldq, const void* K, int64
     YUME_REQUIRE(isfinite(last_key_weight) && last_key_weight >= 1.0f && last_key_weight <= 1048576.0f,
                  "attn_fwd_kw: last_key_weight=%g must be finite and in [1, 2^20]", (double)last_key_weight);
     return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, last_key_weight, stream);
+}
+
+// Sliding-window / causal attention (attn_band.hpp): row i sits at q_pos0 + i on the key axis and sees the keys of attn_band_plan::visible.
+// A window that hides no (row, key) pair of the call IS yume_attn_fwd_ws: same entry, same kernel choice, same bits.
+extern "C" int yume_attn_fwd_band(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                                  int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant, int64_t q_pos0, int64_t win_left,
+                                  int64_t win_right, void* workspace, int64_t workspace_bytes, void* stream) {
+    YUME_REQUIRE(Q && K && Vt && O, "attn_fwd_band: NULL pointer");
+    YUME_REQUIRE(Lq > 0 && Lk > 0 && H > 0, "attn_fwd_band: empty problem Lq=%lld Lk=%lld H=%lld", (long long)Lq, (long long)Lk, (long long)H);
+    YUME_REQUIRE(Lq < (1ll << 30) && Lk < (1ll << 30) && H < 65536, "attn_fwd_band: dimension too large");
+    YUME_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldvt % 8) == 0 && (ldo % 4) == 0, "attn_fwd_band: ldq/ldk/ldvt must be multiples of 8, ldo of 4");
+    YUME_REQUIRE(ldk < (1ll << 24) && ldvt < (1ll << 24), "attn_fwd_band: ldk / ldvt too large for 32-bit tile offsets");
+    YUME_REQUIRE(ldvt >= Lk && ldvt >= 8, "attn_fwd_band: ldvt=%lld must be >= Lk=%lld", (long long)ldvt, (long long)Lk);
+    YUME_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)Vt % 16) == 0 && ((uintptr_t)O % 8) == 0,
+                 "attn_fwd_band: pointer alignment");
+    YUME_REQUIRE(win_left >= -1 && win_right >= -1, "attn_fwd_band: win_left=%lld / win_right=%lld must be >= -1 (-1: unbounded on that side)",
+                 (long long)win_left, (long long)win_right);
+    YUME_REQUIRE(q_pos0 >= -(1ll << 31) && q_pos0 < (1ll << 31), "attn_fwd_band: q_pos0=%lld must be in [-2^31, 2^31)", (long long)q_pos0);
+    const attn_band_plan::Window w{q_pos0, win_left, win_right};
+    if (attn_band_plan::hides_nothing(Lq, Lk, w))
+        return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, stream);
+    const int q_pre = (variant & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (variant & YUME_ATTN_KV_PADDED) != 0;
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 11) {
+        yume_set_error("attn_fwd_band: variant %d has no banded kernel (variants 0 and 11 do)", v);
+        return YUME_EUNSUP;
+    }
+    AttnArgs a{};
+    a.Q = (const unsigned short*)Q; a.ldq = ldq;
+    a.K = (const unsigned short*)K; a.ldk = ldk;
+    a.Vt = (const unsigned short*)Vt; a.ldvt = ldvt;
+    a.O = (unsigned short*)O; a.ldo = ldo;
+    a.Lq = (int)Lq; a.Lk = (int)Lk; a.H = (int)H;
+    a.q_prescaled = q_pre;
+    a.scale_log2 = q_pre ? 1.0f : scale * 1.4426950408889634f;
+    a.accumulate = accumulate;
+    a.splits = 1;
+    a.last_w = 1.0f;
+    if (attn_log_on()) {
+        int64_t tmin = INT64_MAX, tmax = 0;
+        for (int64_t q = 0; q < Lq; q += QB) {
+            const attn_band_plan::TileRange r = attn_band_plan::tile_range(q, (q + QB < Lq ? q + QB : Lq) - 1, Lk, w);
+            const int64_t n = r.hi - r.lo + 1;
+            tmin = n < tmin ? n : tmin;
+            tmax = n > tmax ? n : tmax;
+        }
+        fprintf(stderr, "[attn_fwd_band] band q_pos0=%lld left=%lld right=%lld tiles_min=%lld tiles_max=%lld Lq=%d Lk=%d H=%d ldq=%lld ldk=%lld "
+                        "ldvt=%lld ldo=%lld prescaled=%d kv_padded=%d accumulate=%d\n", (long long)q_pos0, (long long)win_left, (long long)win_right,
+                (long long)tmin, (long long)tmax, a.Lq, a.Lk, a.H, (long long)ldq, (long long)ldk, (long long)ldvt, (long long)ldo, q_pre, kv_pad, accumulate);
+    }
+    attn_band::launch(a, w, (hipStream_t)stream);
+    YUME_CHECK_LAUNCH("attn_fwd_band");
+    return YUME_OK;
 }
 
 // Segmented cross-attention (attn_seg.hpp): nseg independent problems of Lq_seg queries each, seg_pitch rows apart in Q and O, every one with

@@ -119,6 +119,12 @@ class DiTEngine:
         # the pack key: flipping it re-packs.
         self.int8_qkv = os.environ.get("YUME_INT8_QKV", "0") == "1"
         self._int8_qkv_said = False
+        # r26: the model's window_size (left, right) — flash-attn's sliding window on the token axis, -1 = unbounded on that side — for the
+        # self-attention of the single-sample forward (_blocks, its trimmed last block, the block_forward seam and the sequence-parallel call):
+        # token i sees the keys i - left ... i + right (yume_attn_fwd_band). Taken from model.window_size and settable: setting it is how a
+        # checkpoint shipped with (-1, -1) is tried with a window. Cross-attention is never windowed, as in the reference. With a window
+        # fp8_attn keeps the bf16 self-attention, and forward_pair / forward_batch refuse. (-1, -1) = today's calls, bit for bit.
+        self.window_size = tuple(int(v) for v in getattr(model, "window_size", (-1, -1)))
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -441,7 +447,9 @@ class DiTEngine:
                 self._fp8_attn_notice("the sequence-parallel self-attention keeps the bf16 kernels")
                 qf, kf, vtf = self.sp.exchange_qkv(qk, vt, C)
                 of = self._buf("att_sp", (qf.shape[0], qf.shape[1]), torch.bfloat16)
-                ops.attn_fwd(qf, kf, vtf, of, qf.shape[0], n_keys, H // self.sp.world, variant=self.attn_variant, q_prescaled=self.q_prescale)
+                # (after the all-to-all this rank holds ALL tokens of its heads: row 0 is token 0)
+                ops.attn_fwd(qf, kf, vtf, of, qf.shape[0], n_keys, H // self.sp.world, variant=self.attn_variant, q_prescaled=self.q_prescale,
+                             **self._window_args(0))
                 sa = self.sp.exchange_out(of)
             T("gemm_o", ops.gemm_bf16, sa, d["wo"], d["bo"], xs, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=row_idx, variant=self.gemm_variant)
             # --- cross attention
@@ -465,15 +473,36 @@ class DiTEngine:
             if os.environ.get("YUME_ATTN_LOG", "0") not in ("", "0"):
                 sys.stderr.write(f"[fp8_attn] {why}\n")
 
+    def _windowed(self):
+        return tuple(self.window_size) != (-1, -1)
+
+    def _window_args(self, q_pos0):
+        """the window arguments of a self-attention ops.attn_fwd call whose first query row is token q_pos0; none without a window: the call
+        is then the one it always was"""
+        if not self._windowed():
+            return {}
+        left, right = (int(v) for v in self.window_size)
+        if left < -1 or right < -1:
+            raise ValueError(f"DiTEngine.window_size={self.window_size}: -1 (unbounded) or a non-negative width per side")
+        return {"window": (left, right), "q_pos0": int(q_pos0)}
+
+    def _refuse_window(self, who):
+        if self._windowed():
+            raise NotImplementedError(f"{who} does not implement window_size={tuple(self.window_size)}: its self-attention kernels are dense "
+                                      "(set engine.window_size = (-1, -1), or call the single-sample forward per leg / sample)")
+
     def _self_attn_step(self, qk, vt, out, s, L, n_keys):
         """the self-attention of one block of the single-sample forward behind rmsnorm_rope: the queries are the rows [s, L) of qk[:, :C], the
         keys the first n_keys rows of qk[:, C:] and columns of vt; out [L - s, C]. With fp8_attn: quant_rows_mx(qk) + attn_vt_mx(vt) ->
-        attn_fwd_f8mx on engine-owned byte buffers (allocated by the first eager forward); otherwise today's bf16 call."""
+        attn_fwd_f8mx on engine-owned byte buffers (allocated by the first eager forward); otherwise today's bf16 call. With a window_size
+        the bf16 call carries it with q_pos0 = s (row s of the call is token s), and fp8_attn keeps bf16."""
         m = self.model
         C, H = m.dim, m.num_heads
         T = self._timed
         if self.fp8_attn:
-            if C != 128 * H:
+            if self._windowed():
+                self._fp8_attn_notice(f"self-attention stays bf16: window_size={tuple(self.window_size)} runs the bf16 band kernel")
+            elif C != 128 * H:
                 self._fp8_attn_notice(f"self-attention stays bf16: head_dim={C // H} is not 128")
             elif not self.q_prescale or self.attn_variant != 0:
                 self._fp8_attn_notice("self-attention stays bf16: the e4m3 kernel takes pre-scaled q and the automatic variant only")
@@ -489,7 +518,7 @@ class DiTEngine:
                 T("attn_self", ops.attn_fwd_f8mx, qk8[s:, :C], qke[s:, :4 * H], qk8[:, C:], qke[:, 4 * H:], vt8, ev, out, L - s, n_keys, H)
                 return out
         T("attn_self", ops.attn_fwd, qk[s:, :C], qk[:, C:], vt, out, L - s, n_keys, H, variant=self.attn_variant, q_prescaled=self.q_prescale,
-          kv_padded=True)
+          kv_padded=True, **self._window_args(s))
         return out
 
     def _qkv_step(self, d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps):
@@ -822,6 +851,7 @@ class DiTEngine:
 
         cache_context keys on both contexts (and keeps its own K / V^T buffers: forward_one's cache is not disturbed). trim_last_block is
         ignored here: the last block runs on every row. Sequence parallelism and the block-residual cache are not implemented for the pair."""
+        self._refuse_window("forward_pair / forward_cfg")
         if self.sp is not None:
             raise NotImplementedError("forward_pair is not implemented under sequence parallelism (enable_sequence_parallel)")
         self.ensure_packed()
@@ -945,6 +975,7 @@ class DiTEngine:
 
         cache_context keys on all prompts and clip_feas (own buffers: forward_one's and forward_pair's caches are not disturbed);
         trim_last_block is ignored. Sequence parallelism and the block-residual cache are not implemented for the batch."""
+        self._refuse_window("forward_batch")
         B = len(us)
         if len(ts) != B or len(contexts) != B:
             raise RuntimeError(f"forward_batch: {B} samples, {len(ts)} timesteps, {len(contexts)} contexts")

@@ -568,14 +568,20 @@ ATTN_KV_PADDED = 0x200       # YUME_ATTN_KV_PADDED
 
 
 def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False,
-             last_key_weight=1.0):
+             last_key_weight=1.0, window=(-1, -1), q_pos0=0):
     """out[Lq, H*128] = softmax(q k^T * scale) v ; q,k token-major bf16 2-D views, vt K-major [H*128, >=Lk].
     q_prescaled: q already carries scale * log2(e) (`scale` is ignored): out = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j).
     kv_padded: the caller guarantees that k's storage is readable up to ceil(Lk/64)*64 rows and that vt has that many columns with finite
     values behind column Lk (YUME_ATTN_KV_PADDED): with q_prescaled it opens the persistent kernel (attn_fwd8.hip).
     last_key_weight: key Lk - 1 stands for that many identical keys (yume_attn_fwd_kw; variants 0, 2 and 10 = the short-key kernel, Lk <= 128).
-    The weighted export is called only for a weight other than 1 or variant 10; every other call is the one it always was."""
+    The weighted export is called only for a weight other than 1 or variant 10; every other call is the one it always was.
+    window = (left, right), q_pos0: query row i sits at q_pos0 + i on the key axis and sees the keys j with q_pos0 + i - left <= j <= q_pos0 + i +
+    right (-1: unbounded on that side; causal is right = 0; yume_attn_fwd_band, variants 0 and 11, no weighted last key). The banded export is
+    called only for a window other than (-1, -1), and runs the banded kernel only where the window hides a key from a row."""
     lib = _lib.load()
+    window = (int(window[0]), int(window[1]))
+    if window != (-1, -1) and last_key_weight != 1.0:
+        raise RuntimeError("yume_amd.attn_fwd: a window and a last_key_weight != 1 do not combine (yume_attn_fwd_band takes no weighted key)")
     _dev(q, "q", torch.bfloat16)
     _dev(k, "k", torch.bfloat16)
     _dev(vt, "vt", torch.bfloat16)
@@ -611,6 +617,11 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
             if ws is None or ws.numel() < nbytes:
                 ws = _attn_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
     flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
+    if window != (-1, -1):
+        rc = lib.yume_attn_fwd_band(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), window[0],
+                                    window[1], _ptr(ws), nbytes if ws is not None else 0, _stream())
+        _lib.check(rc, "yume_attn_fwd_band")
+        return out
     if last_key_weight != 1.0 or variant == 10:
         rc = lib.yume_attn_fwd_kw(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, _ptr(ws),
                                   nbytes if ws is not None else 0, float(last_key_weight), _stream())
