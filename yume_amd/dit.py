@@ -125,6 +125,12 @@ class DiTEngine:
         # checkpoint shipped with (-1, -1) is tried with a window. Cross-attention is never windowed, as in the reference. With a window
         # fp8_attn keeps the bf16 self-attention, and forward_pair / forward_batch refuse. (-1, -1) = today's calls, bit for bit.
         self.window_size = tuple(int(v) for v in getattr(model, "window_size", (-1, -1)))
+        # r27: a captured hipGraph holds raw pointers to what the engine handed it — the _buf workspaces, the per-clip tables, the packed
+        # weights — and knows nothing of _ws, _plan_cache or P. What a capture was handed is kept here (workspaces once per storage), so a later
+        # eager call at another shape, a flipped pack option or the emptying plan cache replaces the engine's entry but frees nothing a replay
+        # reads or writes. Held until release_captured(); empty, and never looked at, while nothing is captured.
+        self._captured = []
+        self._captured_ids = set()
 
     # ------------------------------------------------------------------ profiling (bench.py)
     def _timed(self, name, fn, *a, **k):
@@ -271,8 +277,22 @@ class DiTEngine:
     def ensure_packed(self):
         key = self._param_key()
         if key != self._packed_key:
+            if self._captured and getattr(self, "P", None) is not None:
+                self._captured.append(self.P)      # (r27) a live graph may replay on the outgoing weights
             self._pack()
             self._packed_key = key
+
+    # ------------------------------------------------------------------ what a graph capture was handed (r27)
+    def _pin(self, obj, ident):
+        if ident not in self._captured_ids:
+            self._captured_ids.add(ident)
+            self._captured.append(obj)
+
+    def release_captured(self):
+        """forget what stream captures were handed (workspaces, per-clip tables, replaced packed weights). Call it after deleting every
+        graph captured from this engine: a graph replayed afterwards may run on memory the engine has given back."""
+        self._captured.clear()
+        self._captured_ids.clear()
 
     # ------------------------------------------------------------------ workspaces / per-clip tables
     def _buf(self, name, shape, dtype, zero=False, grow_rows=False):
@@ -280,12 +300,13 @@ class DiTEngine:
         (rows / columns no kernel writes) has to stay finite. grow_rows: a kept tensor with at least shape[0] rows (and the same other
         dims) serves as its first shape[0] rows — for callers whose row count alternates (the trimmed last block beside the full ones)."""
         t = self._ws.get(name)
-        if grow_rows and t is not None and t.shape[0] >= shape[0] and tuple(t.shape[1:]) == tuple(shape[1:]) and t.dtype == dtype and t.device == self.dev:
-            return t[:shape[0]]
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev:
+        grown = grow_rows and t is not None and t.shape[0] >= shape[0] and tuple(t.shape[1:]) == tuple(shape[1:]) and t.dtype == dtype and t.device == self.dev
+        if not grown and (t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev):
             t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.dev)
             self._ws[name] = t
-        return t
+        if torch.cuda.is_current_stream_capturing():
+            self._pin(t, ("ws", t.untyped_storage().data_ptr()))     # (the base tensor, not the row view)
+        return t[:shape[0]] if grown else t
 
     def _clip_tables(self, key, build):
         v = self._plan_cache.get(key)
@@ -294,6 +315,8 @@ class DiTEngine:
                 self._plan_cache.clear()
             v = build()
             self._plan_cache[key] = v
+        if torch.cuda.is_current_stream_capturing():
+            self._pin(v, ("plan", id(v)))         # (the cache empties itself past 64 clips; a graph still reads the RoPE / selector tables)
         return v
 
     # ------------------------------------------------------------------ pieces

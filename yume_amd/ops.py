@@ -496,6 +496,23 @@ def gemm_f6_mx(a6, ea, w6, ew, bias, out, epi=EPI_F32, gate=None, gate_stride=0,
 # Scratch buffers of the split-K GEMM and the attention key-range split are keyed by (device, stream): two callers on
 # different HIP streams of one device (a VAE decode overlapped with the next chunk's denoise, say) never share partials.
 _splitk_ws = {}
+# r27: each of them (and _attn_ws / _attn_batch_ws below) is REPLACED when a bigger call arrives on its (device, stream), and a hipGraph
+# captured from a smaller call holds the old tensor's raw pointer. The stream in the key does not save it: torch.cuda.graph captures on one
+# shared side stream unless given another, so a second capture at a larger shape, or an eager call on the stream that was captured on, finds
+# the same entry. What a capture was handed is therefore kept here until release_captured().
+_captured = []
+
+
+def _pin_if_capturing(ws):
+    if torch.cuda.is_current_stream_capturing() and not any(ws is c for c in _captured):
+        _captured.append(ws)
+    return ws
+
+
+def release_captured():
+    """forget the scratch tensors stream captures were handed. Call it after deleting every graph captured through this module (the DiT
+    engine's, the encoders'): a graph replayed afterwards may write partials into memory handed to someone else."""
+    _captured.clear()
 
 
 def _ws_key(t):
@@ -534,6 +551,7 @@ def gemm_small_m(a, w, bias, out, epi=EPI_BF16, target_blocks=256):
     if ws is None or ws.numel() < need:
         ws = torch.empty(max(need, 1 << 22), dtype=torch.float32, device=a.device)
         _splitk_ws[key] = ws
+    _pin_if_capturing(ws)
     rc = lib.yume_gemm_bf16_splitk(ap, lda, wp, ldw, _ptr(bias), M, N, K, epi, op, ldo, splits, ws.data_ptr(), _stream())
     _lib.check(rc, "yume_gemm_bf16_splitk")
     return out
@@ -616,6 +634,7 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
             ws = _attn_ws.get(wkey)
             if ws is None or ws.numel() < nbytes:
                 ws = _attn_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+            _pin_if_capturing(ws)
     flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
     if window != (-1, -1):
         rc = lib.yume_attn_fwd_band(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), window[0],
@@ -726,6 +745,7 @@ def attn_fwd_batch(q, k, vt, out, nseg, Lq_seg, q_pitch, Lk_seg, k_pitch, H, sca
             ws = _attn_batch_ws.get(wkey)
             if ws is None or ws.numel() < nbytes:
                 ws = _attn_batch_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+            _pin_if_capturing(ws)
     flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
     rc = lib.yume_attn_fwd_batch(qp, ldq, kp, ldk, vp, ldv, op, ldo, nseg, Lq_seg, q_pitch, Lk_seg, k_pitch, H, scale, 1 if accumulate else 0,
                                  flags, _ptr(ws), ws.numel() if ws is not None else 0, _stream())
