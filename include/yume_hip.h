@@ -404,6 +404,33 @@ int yume_attn_fwd_band(const void* Q, int64_t ldq, const void* K, int64_t ldk, c
                        void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
                        int64_t q_pos0, int64_t win_left, int64_t win_right,
                        void* workspace, int64_t workspace_bytes, void* stream);
+/* FRAME-WINDOW / FRAME-CAUSAL form (r28; a function added, no argument list changed: ABI 9). The key axis is partitioned into blocks — the
+ * frames of a video sequence — by nspan (1 .. 16) uniform spans: span g starts at row row0_g (row0_0 = 0, row0_{g+1} = row0_g + span_rows[g] *
+ * span_blocks[g]) and holds span_blocks[g] blocks of span_rows[g] rows each; N rows and NB blocks in all, numbered through the spans in order.
+ * b(p) = the block of position p. Row i of the call sits at pos(i) = q_pos0 + i and
+ *   visible(i, j)  <=>  0 <= j < Lk  and  (back < 0 or b(j) >= b(pos(i)) - back)  and  (ahead < 0 or b(j) <= b(pos(i)) + ahead)
+ *   O[h,i,:] = exact softmax over the visible keys;  O[h,i,:] = 0 where row i sees no key (an accumulate call then leaves the old O[h,i,:] as
+ *   it is, bit for bit): yume_attn_fwd_band's rules. A row's visible set is one interval, start(max(b - back, 0)) ... min(end(min(b + ahead,
+ *   NB - 1)), Lk) - 1. back / ahead: -1 = unbounded on that side; (-1, 0) is the frame-causal (block-causal) mask.
+ * replaces: nothing the reference computes — wan23/modules/model.py runs global self-attention over the FramePack sequence; this is the
+ *           frame-aligned form of the window of wan23/modules/attention.py:24-130 flash_attention(window_size=), which counts tokens and so
+ *           cuts frames part-way and spans dozens of frames in a coarse history group (yume_amd/framepack.py frame_spans gives the partition).
+ * span_rows / span_blocks: HOST arrays of nspan entries, read during the call and handed to the kernel by value (no device memory, nothing a
+ *    stream capture could lose), as yume_attn_fwd_seg's arrays.
+ * Checks (YUME_EINVAL by name `attn_fwd_fband`): everything yume_attn_fwd_ws checks; nspan in [1, 16]; every span_rows[g], span_blocks[g] >= 1;
+ *    N < 2^31; back, ahead >= -1; 0 <= q_pos0; q_pos0 + Lq <= N; Lk <= N.
+ * A (partition, back, ahead, q_pos0) that hides no (i, j) pair of the call IS yume_attn_fwd_ws with the same arguments: same kernel choice, same
+ *    log line, same bits. One span of one-row blocks computes yume_attn_fwd_band(win_left = back, win_right = ahead), bit for bit. Only a call
+ *    that hides at least one pair runs the kernel (attn_fband.hpp: attn_band_kernel's walk, each lane's key interval from its row's block):
+ *    variant 0 and variant 12 = that kernel; any other variant: YUME_EUNSUP (the message names it).
+ * accumulate, ragged Lq, both scale modes and YUME_ATTN_KV_PADDED (accepted; it changes nothing here) as for yume_attn_fwd. No weighted last
+ *    key, no key-range split; the workspace is handed on to yume_attn_fwd_ws and otherwise unused.
+ * env YUME_ATTN_LOG=1: one line per banded call, `[attn_fwd_fband] fband q_pos0=.. back=.. ahead=.. nspan=.. nblocks=.. tiles_min=..
+ *    tiles_max=.. Lq=.. Lk=.. H=.. ...` (the fewest and the most key tiles a workgroup walks). tests/test_attn_fband_routes_gpu.py reads it. */
+int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                        void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
+                        int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 /* SEGMENTED form (r9): ONE launch serves nseg (1 .. 8) independent attention problems that share Q's and O's buffers and every shape but the
  * key count. Segment s owns the query rows [s * seg_pitch, s * seg_pitch + Lq_seg) of Q and O (seg_pitch >= Lq_seg, in rows; the rows of the
  * gap are neither read nor written) and attends over its own K[s] / Vt[s] (Lk[s] keys, key Lk[s] - 1 counting last_key_weight[s] times).

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 
-__all__ = ["flash_attention", "attention"]
+__all__ = ["flash_attention", "attention", "frame_window_attention"]
 
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
@@ -32,6 +32,11 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         right = 0
     if dtype != torch.bfloat16:
         raise NotImplementedError("yume_amd.flash_attention computes in bf16 (the reference default)")
+    return _attend(q, k, v, q_lens, k_lens, softmax_scale, q_scale, lambda nq, nk: dict(window=(left, right), q_pos0=nk - nq))
+
+
+def _attend(q, k, v, q_lens, k_lens, softmax_scale, q_scale, mask):
+    """the seam's body: per sample one ops.attn_fwd call with the mask arguments mask(nq, nk) gives"""
     b, lq, n, d = q.shape
     lk = k.size(1)
     if k.size(2) != n or v.size(-1) != d:
@@ -61,10 +66,26 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vi = vi.float()
         vt = torch.empty((n * d, (nk + 7) // 8 * 8), dtype=torch.bfloat16, device=q.device)
         ops.transpose_bf16(vi.contiguous(), vt)
-        ops.attn_fwd(qi, ki, vt, out[i, :nq], nq, nk, n, scale=scale, window=(left, right), q_pos0=nk - nq)
+        ops.attn_fwd(qi, ki, vt, out[i, :nq], nq, nk, n, scale=scale, **mask(nq, nk))
         if nq < lq:
             out[i, nq:].zero_()   # flash-attn's varlen packing leaves padded queries out; the reference never reads them
     return out.view(b, lq, n, d)[..., :d_in].type(out_dtype)
+
+
+def frame_window_attention(q, k, v, spans, frame_window, q_lens=None, k_lens=None, softmax_scale=None):
+    """flash_attention's tensor conventions (q [B, Lq, N, d], k / v [B, Lk, N, d], optional per-sample lengths, bf16 compute, the output in
+    q's dtype) under a FRAME-aligned window: spans = [(rows, blocks), ...] partitions the key axis into frames (framepack.frame_spans), and a
+    query sees every key of the frames within frame_window = (back, ahead) of its own (-1: unbounded; (-1, 0): frame-causal). Rows are
+    bottom-right aligned per sample as in flash_attention: query row i sits at (nk - nq) + i. A row that sees no key is 0; a window that hides
+    nothing is the global call, bit for bit. A function of its own: flash_attention's signature is the reference's."""
+    assert q.device.type == "cuda" and q.size(-1) <= 256
+    back, ahead = int(frame_window[0]), int(frame_window[1])
+    if back < -1 or ahead < -1:
+        raise ValueError(f"yume_amd.frame_window_attention: frame_window={tuple(frame_window)}: -1 (unbounded) or a non-negative frame count "
+                         "per side")
+    spans = [(int(r), int(b)) for r, b in spans]
+    return _attend(q, k, v, q_lens, k_lens, softmax_scale, None,
+                   lambda nq, nk: dict(frame_window=(back, ahead), spans=spans, q_pos0=nk - nq))
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,

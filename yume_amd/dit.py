@@ -125,6 +125,15 @@ class DiTEngine:
         # checkpoint shipped with (-1, -1) is tried with a window. Cross-attention is never windowed, as in the reference. With a window
         # fp8_attn keeps the bf16 self-attention, and forward_pair / forward_batch refuse. (-1, -1) = today's calls, bit for bit.
         self.window_size = tuple(int(v) for v in getattr(model, "window_size", (-1, -1)))
+        # r28: a FRAME-aligned window for the same self-attention calls: None, or (back, ahead) — a token sees every token of the frames within
+        # `back` frames before and `ahead` frames after its own, -1 = unbounded on that side, (-1, 0) = frame-causal (yume_attn_fwd_fband). The
+        # frames are those of the clip's own plan (framepack.frame_spans of the object the RoPE table was built from): on a FramePack sequence
+        # one span per group, a coarse history frame being a few tokens and a new frame hundreds — what window_size, counting tokens, cannot
+        # say. Not combined with a window_size; fp8_attn keeps bf16 under it; forward_pair / forward_batch refuse. None = today's calls, bit
+        # for bit (no new code is reached); env YUME_FRAME_WINDOW="back,ahead" sets it.
+        fw = os.environ.get("YUME_FRAME_WINDOW", "").strip()
+        self.frame_window = tuple(int(v) for v in fw.split(",")) if fw else None
+        self._spans = None            # the current clip's (rows, blocks) spans, kept by _prologue while frame_window is set
         # r27: a captured hipGraph holds raw pointers to what the engine handed it — the _buf workspaces, the per-clip tables, the packed
         # weights — and knows nothing of _ws, _plan_cache or P. What a capture was handed is kept here (workspaces once per storage), so a later
         # eager call at another shape, a flipped pack option or the emptying plan cache replaces the engine's entry but frees nothing a replay
@@ -472,7 +481,7 @@ class DiTEngine:
                 of = self._buf("att_sp", (qf.shape[0], qf.shape[1]), torch.bfloat16)
                 # (after the all-to-all this rank holds ALL tokens of its heads: row 0 is token 0)
                 ops.attn_fwd(qf, kf, vtf, of, qf.shape[0], n_keys, H // self.sp.world, variant=self.attn_variant, q_prescaled=self.q_prescale,
-                             **self._window_args(0))
+                             **self._window_args(0), **self._frame_args(0, qf.shape[0]))
                 sa = self.sp.exchange_out(of)
             T("gemm_o", ops.gemm_bf16, sa, d["wo"], d["bo"], xs, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=row_idx, variant=self.gemm_variant)
             # --- cross attention
@@ -509,6 +518,33 @@ class DiTEngine:
             raise ValueError(f"DiTEngine.window_size={self.window_size}: -1 (unbounded) or a non-negative width per side")
         return {"window": (left, right), "q_pos0": int(q_pos0)}
 
+    def _frame_args(self, q_pos0, n_rows=None):
+        """the frame-window arguments of a self-attention ops.attn_fwd call whose first query row is token q_pos0; none without a
+        frame_window. n_rows: the call's query rows where they outnumber the clip's tokens (the sequence-parallel pad rows): the rows behind
+        the last token are one more block, seen by nobody (they lie behind Lk)."""
+        if self.frame_window is None:
+            return {}
+        if self._windowed():
+            raise ValueError(f"DiTEngine.frame_window={tuple(self.frame_window)} and window_size={tuple(self.window_size)} do not combine: "
+                             "one mask per self-attention (set one of them back to None / (-1, -1))")
+        fw = tuple(int(v) for v in self.frame_window)
+        if len(fw) != 2 or fw[0] < -1 or fw[1] < -1:
+            raise ValueError(f"DiTEngine.frame_window={self.frame_window}: None, or (back, ahead) with -1 (unbounded) or a non-negative frame "
+                             "count per side")
+        if self._spans is None:
+            raise NotImplementedError(f"frame_window={fw} needs the clip's frame partition, which block_forward's bare rows do not carry (run "
+                                      "the model's forward, or set engine.frame_window = None)")
+        spans = list(self._spans)
+        n_tok = sum(r * b for r, b in spans)
+        if n_rows is not None and n_rows > n_tok:
+            spans.append((n_rows - n_tok, 1))
+        return {"frame_window": fw, "spans": spans, "q_pos0": int(q_pos0)}
+
+    def _refuse_frame_window(self, who):
+        if self.frame_window is not None:
+            raise NotImplementedError(f"{who} does not implement frame_window={tuple(self.frame_window)}: its self-attention kernels are dense "
+                                      "(set engine.frame_window = None, or call the single-sample forward per leg / sample)")
+
     def _refuse_window(self, who):
         if self._windowed():
             raise NotImplementedError(f"{who} does not implement window_size={tuple(self.window_size)}: its self-attention kernels are dense "
@@ -518,13 +554,15 @@ class DiTEngine:
         """the self-attention of one block of the single-sample forward behind rmsnorm_rope: the queries are the rows [s, L) of qk[:, :C], the
         keys the first n_keys rows of qk[:, C:] and columns of vt; out [L - s, C]. With fp8_attn: quant_rows_mx(qk) + attn_vt_mx(vt) ->
         attn_fwd_f8mx on engine-owned byte buffers (allocated by the first eager forward); otherwise today's bf16 call. With a window_size
-        the bf16 call carries it with q_pos0 = s (row s of the call is token s), and fp8_attn keeps bf16."""
+        the bf16 call carries it with q_pos0 = s (row s of the call is token s), and fp8_attn keeps bf16; a frame_window likewise."""
         m = self.model
         C, H = m.dim, m.num_heads
         T = self._timed
         if self.fp8_attn:
             if self._windowed():
                 self._fp8_attn_notice(f"self-attention stays bf16: window_size={tuple(self.window_size)} runs the bf16 band kernel")
+            elif self.frame_window is not None:
+                self._fp8_attn_notice(f"self-attention stays bf16: frame_window={tuple(self.frame_window)} runs the bf16 frame-band kernel")
             elif C != 128 * H:
                 self._fp8_attn_notice(f"self-attention stays bf16: head_dim={C // H} is not 128")
             elif not self.q_prescale or self.attn_variant != 0:
@@ -541,7 +579,7 @@ class DiTEngine:
                 T("attn_self", ops.attn_fwd_f8mx, qk8[s:, :C], qke[s:, :4 * H], qk8[:, C:], qke[:, 4 * H:], vt8, ev, out, L - s, n_keys, H)
                 return out
         T("attn_self", ops.attn_fwd, qk[s:, :C], qk[:, C:], vt, out, L - s, n_keys, H, variant=self.attn_variant, q_prescaled=self.q_prescale,
-          kv_padded=True, **self._window_args(s))
+          kv_padded=True, **self._window_args(s), **self._frame_args(s))
         return out
 
     def _qkv_step(self, d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps):
@@ -705,6 +743,7 @@ class DiTEngine:
         if n_rope == 0:
             rope_cs = torch.zeros((1, 64, 2), dtype=torch.float32, device=self.dev)
         self._ctx_key = None                                     # the per-conditioning cache belongs to forward_one
+        self._spans = None                                       # (bare rows: no frame partition — a frame_window refuses by name)
         self._blocks(xs, L, tab.view(1, R, 6, C), row_idx, R, rope_cs.to(self.dev).contiguous(), n_rope, ctx, n_img, True, only=[i])
         return xs.clone()
 
@@ -762,6 +801,8 @@ class DiTEngine:
             plan, rope, ridx = self._clip_tables(("p", F, H, W, lfz, n_sel), build)
             L, n_hist = plan.seq_len, plan.n_hist_tok
             groups, grid = plan.groups, plan.new_grid
+            if self.frame_window is not None:
+                self._spans = framepack.frame_spans(plan)
         else:
             def build():
                 if H % 2 or W % 2:
@@ -774,6 +815,8 @@ class DiTEngine:
             g0, rope = self._clip_tables(("u", F, H, W), build)
             L, n_hist = g0.ntok, 0
             groups, grid = [g0], (F, g0.hp, g0.wp)
+            if self.frame_window is not None:
+                self._spans = framepack.frame_spans(g0)
             ridx = None
 
         # --- timestep rows
@@ -875,6 +918,7 @@ class DiTEngine:
         cache_context keys on both contexts (and keeps its own K / V^T buffers: forward_one's cache is not disturbed). trim_last_block is
         ignored here: the last block runs on every row. Sequence parallelism and the block-residual cache are not implemented for the pair."""
         self._refuse_window("forward_pair / forward_cfg")
+        self._refuse_frame_window("forward_pair / forward_cfg")
         if self.sp is not None:
             raise NotImplementedError("forward_pair is not implemented under sequence parallelism (enable_sequence_parallel)")
         self.ensure_packed()
@@ -999,6 +1043,7 @@ class DiTEngine:
         cache_context keys on all prompts and clip_feas (own buffers: forward_one's and forward_pair's caches are not disturbed);
         trim_last_block is ignored. Sequence parallelism and the block-residual cache are not implemented for the batch."""
         self._refuse_window("forward_batch")
+        self._refuse_frame_window("forward_batch")
         B = len(us)
         if len(ts) != B or len(contexts) != B:
             raise RuntimeError(f"forward_batch: {B} samples, {len(ts)} timesteps, {len(contexts)} contexts")

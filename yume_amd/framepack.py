@@ -135,3 +135,19 @@ def plan_rope(plan: PackPlan, head_dim: int) -> torch.Tensor:
         grids.append((f_off, g.nf, g.hp, g.wp))
         f_off += g.nf
     return rope_cos_sin(grids, head_dim)
+
+
+def frame_spans(plan) -> List[Tuple[int, int]]:
+    """The frame partition of a clip's token axis as uniform spans [(rows, blocks)] in token order: `blocks` frames of `rows` tokens each
+    (ops.attn_fwd(frame_window=, spans=), yume_attn_fwd_fband). Built from what the RoPE table is built from:
+      a PackPlan        one span per group in packed order — (hp * wp, nf): a history group's frames at its own pyramid level, then the
+                        new frames;
+      a Group           the plain latent's single group: one span;
+      (F, H, W)         a plain latent by its shape: one span ((H / 2)(W / 2), F)."""
+    if isinstance(plan, PackPlan):
+        return [(g.hp * g.wp, g.nf) for g in plan.groups]
+    if isinstance(plan, Group):
+        return [(plan.hp * plan.wp, plan.nf)]
+    f, h, w = (int(v) for v in plan)
+    hp, wp = _grid(h, w, 0)
+    return [(hp * wp, f)]

@@ -586,7 +586,7 @@ ATTN_KV_PADDED = 0x200       # YUME_ATTN_KV_PADDED
 
 
 def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False,
-             last_key_weight=1.0, window=(-1, -1), q_pos0=0):
+             last_key_weight=1.0, window=(-1, -1), q_pos0=0, frame_window=None, spans=None):
     """out[Lq, H*128] = softmax(q k^T * scale) v ; q,k token-major bf16 2-D views, vt K-major [H*128, >=Lk].
     q_prescaled: q already carries scale * log2(e) (`scale` is ignored): out = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j).
     kv_padded: the caller guarantees that k's storage is readable up to ceil(Lk/64)*64 rows and that vt has that many columns with finite
@@ -595,9 +595,23 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     The weighted export is called only for a weight other than 1 or variant 10; every other call is the one it always was.
     window = (left, right), q_pos0: query row i sits at q_pos0 + i on the key axis and sees the keys j with q_pos0 + i - left <= j <= q_pos0 + i +
     right (-1: unbounded on that side; causal is right = 0; yume_attn_fwd_band, variants 0 and 11, no weighted last key). The banded export is
-    called only for a window other than (-1, -1), and runs the banded kernel only where the window hides a key from a row."""
+    called only for a window other than (-1, -1), and runs the banded kernel only where the window hides a key from a row.
+    frame_window = (back, ahead), spans = [(rows, blocks), ...], q_pos0: the key axis is partitioned into blocks (frames) by the spans in order,
+    `blocks` blocks of `rows` rows each; query row i sits at q_pos0 + i and sees every key of the blocks within `back` before and `ahead` after
+    its own (-1: unbounded on that side; (-1, 0) is frame-causal; yume_attn_fwd_fband, variants 0 and 12, no weighted last key, no token
+    window beside it). None (the default): the call is the one it always was."""
     lib = _lib.load()
     window = (int(window[0]), int(window[1]))
+    if frame_window is not None:
+        if window != (-1, -1):
+            raise RuntimeError("yume_amd.attn_fwd: frame_window and window do not combine (one mask per call)")
+        if last_key_weight != 1.0:
+            raise RuntimeError("yume_amd.attn_fwd: a frame_window and a last_key_weight != 1 do not combine (yume_attn_fwd_fband takes no weighted key)")
+        if spans is None:
+            raise RuntimeError("yume_amd.attn_fwd: frame_window needs spans = [(rows, blocks), ...] (yume_amd.framepack.frame_spans)")
+        spans = [(int(r), int(b)) for r, b in spans]
+    elif spans is not None:
+        raise RuntimeError("yume_amd.attn_fwd: spans without a frame_window")
     if window != (-1, -1) and last_key_weight != 1.0:
         raise RuntimeError("yume_amd.attn_fwd: a window and a last_key_weight != 1 do not combine (yume_attn_fwd_band takes no weighted key)")
     _dev(q, "q", torch.bfloat16)
@@ -636,6 +650,14 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
                 ws = _attn_ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
             _pin_if_capturing(ws)
     flags = variant | (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_KV_PADDED if kv_padded else 0)
+    if frame_window is not None:
+        import ctypes
+        arr = ctypes.c_int64 * max(len(spans), 1)          # host arrays: read during the call, handed to the kernel by value
+        rc = lib.yume_attn_fwd_fband(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), len(spans),
+                                     arr(*[r for r, _ in spans]), arr(*[b for _, b in spans]), int(frame_window[0]), int(frame_window[1]),
+                                     _ptr(ws), nbytes if ws is not None else 0, _stream())
+        _lib.check(rc, "yume_attn_fwd_fband")
+        return out
     if window != (-1, -1):
         rc = lib.yume_attn_fwd_band(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), window[0],
                                     window[1], _ptr(ws), nbytes if ws is not None else 0, _stream())
