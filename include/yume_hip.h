@@ -431,6 +431,28 @@ int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, int64_t ldk, 
                         void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
                         int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead,
                         void* workspace, int64_t workspace_bytes, void* stream);
+/* FRAME-WINDOW form WITH A SINK (r29; a function added, no argument list changed: ABI 9). yume_attn_fwd_fband's partition, pos(i), b(p), back
+ * and ahead, and one more integer: the first `sink` blocks (0 <= sink <= NB) are seen by every row —
+ *   visible(i, j)  <=>  0 <= j < Lk  and  ( b(j) < sink  or  yume_attn_fwd_fband's visible(i, j) )
+ *   With send = min(start(sink), Lk) (start(NB) = N) a row sees [0, send) U [klo(i), khi(i)], klo / khi being yume_attn_fwd_fband's interval:
+ *   one interval where klo(i) <= send, two with a hidden gap otherwise. O, the empty row (none with sink >= 1) and accumulate as there.
+ * replaces: nothing the reference computes. It is what makes the frame window usable on the sequences of wan23/modules/model.py's FramePack
+ *           forward, whose first block is the clip's first frame (yume_amd/framepack.py history_groups: the I2V conditioning image, the anchor
+ *           of the long-video loop): the "attention sink" / anchor frames that windowed video attention pairs with a local window.
+ * Checks (YUME_EINVAL by name `attn_fwd_fsink`): everything yume_attn_fwd_fband checks; 0 <= sink <= NB.
+ * Normalisations: a call that hides no (i, j) pair IS yume_attn_fwd_ws with the same arguments (same kernel choice, log line and bits); sink == 0,
+ *    or a sink that shows no pair the window hides, IS yume_attn_fwd_fband with the same arguments (same log line, same bits, its variants).
+ *    Only a call whose sink adds a pair runs the kernel (attn_fsink.hpp: a walk over the ascending tile LIST sink tiles + band tiles, the
+ *    prefetch following the list across the jump, a two-interval mask): variant 0 and variant 13 = that kernel; any other variant:
+ *    YUME_EUNSUP (the message names it).
+ * accumulate, ragged Lq, both scale modes, YUME_ATTN_KV_PADDED and the workspace as for yume_attn_fwd_fband.
+ * env YUME_ATTN_LOG=1: one line per call that runs the kernel, `[attn_fwd_fsink] fsink q_pos0=.. back=.. ahead=.. sink=.. sink_rows=.. nspan=..
+ *    nblocks=.. tiles_min=.. tiles_max=.. Lq=.. Lk=.. H=.. ...` (sink_rows = send; the fewest and the most key tiles a workgroup walks).
+ *    tests/test_attn_fsink_routes_gpu.py reads it. */
+int yume_attn_fwd_fsink(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                        void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
+                        int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead,
+                        int64_t sink, void* workspace, int64_t workspace_bytes, void* stream);
 /* SEGMENTED form (r9): ONE launch serves nseg (1 .. 8) independent attention problems that share Q's and O's buffers and every shape but the
  * key count. Segment s owns the query rows [s * seg_pitch, s * seg_pitch + Lq_seg) of Q and O (seg_pitch >= Lq_seg, in rows; the rows of the
  * gap are neither read nor written) and attends over its own K[s] / Vt[s] (Lk[s] keys, key Lk[s] - 1 counting last_key_weight[s] times).

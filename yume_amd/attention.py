@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 
-__all__ = ["flash_attention", "attention", "frame_window_attention"]
+__all__ = ["flash_attention", "attention", "frame_window_attention", "frame_sink_attention"]
 
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
@@ -78,14 +78,29 @@ def frame_window_attention(q, k, v, spans, frame_window, q_lens=None, k_lens=Non
     query sees every key of the frames within frame_window = (back, ahead) of its own (-1: unbounded; (-1, 0): frame-causal). Rows are
     bottom-right aligned per sample as in flash_attention: query row i sits at (nk - nq) + i. A row that sees no key is 0; a window that hides
     nothing is the global call, bit for bit. A function of its own: flash_attention's signature is the reference's."""
+    return _frame_attend("frame_window_attention", q, k, v, spans, frame_window, 0, q_lens, k_lens, softmax_scale)
+
+
+def frame_sink_attention(q, k, v, spans, frame_window, sink, q_lens=None, k_lens=None, softmax_scale=None):
+    """frame_window_attention with an always-visible sink: every query also sees the first `sink` frames of the partition (0 <= sink <= the
+    partition's frames; yume_attn_fwd_fsink) — the clip's first frame under FramePack, the anchor a local window would hide. sink = 0 is
+    frame_window_attention, bit for bit. A function of its own: frame_window_attention's signature is held by its tests."""
+    sink = int(sink)
+    if sink < 0:
+        raise ValueError(f"yume_amd.frame_sink_attention: sink={sink}: a non-negative count of leading frames")
+    return _frame_attend("frame_sink_attention", q, k, v, spans, frame_window, sink, q_lens, k_lens, softmax_scale)
+
+
+def _frame_attend(who, q, k, v, spans, frame_window, sink, q_lens, k_lens, softmax_scale):
     assert q.device.type == "cuda" and q.size(-1) <= 256
     back, ahead = int(frame_window[0]), int(frame_window[1])
     if back < -1 or ahead < -1:
-        raise ValueError(f"yume_amd.frame_window_attention: frame_window={tuple(frame_window)}: -1 (unbounded) or a non-negative frame count "
+        raise ValueError(f"yume_amd.{who}: frame_window={tuple(frame_window)}: -1 (unbounded) or a non-negative frame count "
                          "per side")
     spans = [(int(r), int(b)) for r, b in spans]
+    extra = {"frame_sink": sink} if sink else {}
     return _attend(q, k, v, q_lens, k_lens, softmax_scale, None,
-                   lambda nq, nk: dict(frame_window=(back, ahead), spans=spans, q_pos0=nk - nq))
+                   lambda nq, nk: dict(frame_window=(back, ahead), spans=spans, q_pos0=nk - nq, **extra))
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,

@@ -49,9 +49,12 @@ __device__ __forceinline__ void dma_tile_band(DmaBand& dp, int64_t k_round, int6
     dp.v += KT;
 }
 
-// klo / khi: this lane's row sees the keys klo ... khi (already cut to [0, Lk - 1]; klo > khi: none)
+// klo / khi: this lane's row sees the keys klo ... khi (already cut to [0, Lk - 1]; klo > khi: none). SINK (attn_fsink.hpp): and the keys
+// below `send` as well, a second interval; without it the instances are the ones they were.
+template <bool SINK = false>
 __device__ __forceinline__ void tile_body_band(const char* kb, const AttnArgs& p, const bf16x8_t (&qf)[8], f32x16 (&oacc)[4], float& m_run,
-                                               float& l_run, int j0, int ql, int hi, int klo, int khi, const int (&koff)[8], const int (&voff)[4]) {
+                                               float& l_run, int j0, int ql, int hi, int klo, int khi, const int (&koff)[8], const int (&voff)[4],
+                                               int send = 0) {
     const char* vb = kb + K_TILE_BYTES;
     f32x16 sacc[2];
     s_tile(kb, qf, sacc, koff);
@@ -64,7 +67,7 @@ __device__ __forceinline__ void tile_body_band(const char* kb, const AttnArgs& p
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = kbase + 32 * b + (r & 3) + 8 * (r >> 2);
-            const bool v = key >= klo && key <= khi;
+            const bool v = (SINK && key < send) || (key >= klo && key <= khi);
             vis |= v ? (1u << (16 * b + r)) : 0u;
             mx = fmaxf(mx, v ? sacc[b][r] : NEG_BIG);
         }

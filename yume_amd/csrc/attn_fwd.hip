@@ -17,7 +17,8 @@
 // yume_attn_fwd_batch (several stacked self-attention problems of one shape) has attn_fwd_kernel_v8's: attn_batch8.hip.
 // yume_attn_fwd_band (sliding-window / causal attention) has the banded form of attn_fwd_kernel_v2: attn_band.hpp, planned by attn_band_plan.hpp.
 // yume_attn_fwd_fband (frame-window / frame-causal attention over a block partition) has that walk with another interval source: attn_fband.hpp,
-// planned by attn_fband_plan.hpp.
+// planned by attn_fband_plan.hpp. yume_attn_fwd_fsink adds an always-visible sink of leading blocks: a walk over a tile LIST, attn_fsink.hpp,
+// planned by attn_fsink_plan.hpp.
 // and attn_combine_kernel (attn_combine.hpp) merges the key-range pieces of a split v7 / v8 launch, planned by attn_plan.hpp.
 // The transposed formulation and the tile layouts the kernels share: attn_tile.hpp.
 #include "common.hpp"
@@ -33,6 +34,7 @@
 #include "attn_seg.hpp"
 #include "attn_band.hpp"
 #include "attn_fband.hpp"
+#include "attn_fsink.hpp"
 #include <math.h>
 
 static_assert(attn_plan::QBLOCK == QB4 && attn_plan::KTILE == KT && attn_plan::HDIM == D, "attn_plan.hpp restates the tile constants");
@@ -322,50 +324,44 @@ extern "C" int yume_attn_fwd_band(const void* Q, int64_t ldq, const void* K, int
     return YUME_OK;
 }
 
-// Frame-window / frame-causal attention (attn_fband.hpp): the key axis is partitioned into blocks by nspan uniform spans (host arrays, copied
-// into the kernel arguments); row i sits at q_pos0 + i and sees every key of the blocks within `back` before and `ahead` after its own
-// (attn_fband_plan::visible). A (partition, back, ahead, q_pos0) that hides no (row, key) pair of the call IS yume_attn_fwd_ws.
-extern "C" int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
-                                   int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant, int64_t q_pos0, int64_t nspan,
-                                   const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead, void* workspace,
-                                   int64_t workspace_bytes, void* stream) {
-    YUME_REQUIRE(Q && K && Vt && O && span_rows && span_blocks, "attn_fwd_fband: NULL pointer");
-    YUME_REQUIRE(Lq > 0 && Lk > 0 && H > 0, "attn_fwd_fband: empty problem Lq=%lld Lk=%lld H=%lld", (long long)Lq, (long long)Lk, (long long)H);
-    YUME_REQUIRE(Lq < (1ll << 30) && Lk < (1ll << 30) && H < 65536, "attn_fwd_fband: dimension too large");
-    YUME_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldvt % 8) == 0 && (ldo % 4) == 0, "attn_fwd_fband: ldq/ldk/ldvt must be multiples of 8, ldo of 4");
-    YUME_REQUIRE(ldk < (1ll << 24) && ldvt < (1ll << 24), "attn_fwd_fband: ldk / ldvt too large for 32-bit tile offsets");
-    YUME_REQUIRE(ldvt >= Lk && ldvt >= 8, "attn_fwd_fband: ldvt=%lld must be >= Lk=%lld", (long long)ldvt, (long long)Lk);
+// the argument checks of yume_attn_fwd_fband and yume_attn_fwd_fsink, answered under the caller's name; fills the plan, N and NB
+static int fband_check(const char* who, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                       int64_t Lq, int64_t Lk, int64_t H, int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks,
+                       int64_t back, int64_t ahead, attn_fband_plan::Plan& w, int64_t& N, int64_t& NB) {
+    YUME_REQUIRE(Q && K && Vt && O && span_rows && span_blocks, "%s: NULL pointer", who);
+    YUME_REQUIRE(Lq > 0 && Lk > 0 && H > 0, "%s: empty problem Lq=%lld Lk=%lld H=%lld", who, (long long)Lq, (long long)Lk, (long long)H);
+    YUME_REQUIRE(Lq < (1ll << 30) && Lk < (1ll << 30) && H < 65536, "%s: dimension too large", who);
+    YUME_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldvt % 8) == 0 && (ldo % 4) == 0, "%s: ldq/ldk/ldvt must be multiples of 8, ldo of 4", who);
+    YUME_REQUIRE(ldk < (1ll << 24) && ldvt < (1ll << 24), "%s: ldk / ldvt too large for 32-bit tile offsets", who);
+    YUME_REQUIRE(ldvt >= Lk && ldvt >= 8, "%s: ldvt=%lld must be >= Lk=%lld", who, (long long)ldvt, (long long)Lk);
     YUME_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)Vt % 16) == 0 && ((uintptr_t)O % 8) == 0,
-                 "attn_fwd_fband: pointer alignment");
-    YUME_REQUIRE(nspan >= 1 && nspan <= attn_fband_plan::MAX_SPANS, "attn_fwd_fband: nspan=%lld must be in [1, %d]", (long long)nspan,
+                 "%s: pointer alignment", who);
+    YUME_REQUIRE(nspan >= 1 && nspan <= attn_fband_plan::MAX_SPANS, "%s: nspan=%lld must be in [1, %d]", who, (long long)nspan,
                  attn_fband_plan::MAX_SPANS);
-    attn_fband_plan::Plan w{};
+    w = attn_fband_plan::Plan{};
     w.q_pos0 = q_pos0; w.back = back; w.ahead = ahead; w.nspan = (int32_t)nspan;
-    int64_t N = 0, NB = 0;
+    N = 0; NB = 0;
     for (int g = 0; g < (int)nspan; ++g) {
-        YUME_REQUIRE(span_rows[g] >= 1 && span_blocks[g] >= 1, "attn_fwd_fband: span %d: span_rows=%lld and span_blocks=%lld must be >= 1", g,
+        YUME_REQUIRE(span_rows[g] >= 1 && span_blocks[g] >= 1, "%s: span %d: span_rows=%lld and span_blocks=%lld must be >= 1", who, g,
                      (long long)span_rows[g], (long long)span_blocks[g]);
         YUME_REQUIRE(span_rows[g] < (1ll << 31) && span_blocks[g] < (1ll << 31) && N + span_rows[g] * span_blocks[g] < (1ll << 31),
-                     "attn_fwd_fband: the partition's N must be below 2^31 rows (span %d)", g);
+                     "%s: the partition's N must be below 2^31 rows (span %d)", who, g);
         N += span_rows[g] * span_blocks[g];
         NB += span_blocks[g];
         w.rows[g] = (int32_t)span_rows[g];
         w.nblk[g] = (int32_t)span_blocks[g];
     }
-    YUME_REQUIRE(back >= -1 && ahead >= -1, "attn_fwd_fband: back=%lld / ahead=%lld must be >= -1 (-1: unbounded on that side)", (long long)back,
+    YUME_REQUIRE(back >= -1 && ahead >= -1, "%s: back=%lld / ahead=%lld must be >= -1 (-1: unbounded on that side)", who, (long long)back,
                  (long long)ahead);
-    YUME_REQUIRE(q_pos0 >= 0, "attn_fwd_fband: q_pos0=%lld must be >= 0", (long long)q_pos0);
-    YUME_REQUIRE(q_pos0 + Lq <= N, "attn_fwd_fband: q_pos0=%lld + Lq=%lld rows end behind the partition's N=%lld", (long long)q_pos0, (long long)Lq,
+    YUME_REQUIRE(q_pos0 >= 0, "%s: q_pos0=%lld must be >= 0", who, (long long)q_pos0);
+    YUME_REQUIRE(q_pos0 + Lq <= N, "%s: q_pos0=%lld + Lq=%lld rows end behind the partition's N=%lld", who, (long long)q_pos0, (long long)Lq,
                  (long long)N);
-    YUME_REQUIRE(Lk <= N, "attn_fwd_fband: Lk=%lld keys exceed the partition's N=%lld", (long long)Lk, (long long)N);
-    if (attn_fband_plan::hides_nothing(Lq, Lk, w))
-        return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, stream);
-    const int q_pre = (variant & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (variant & YUME_ATTN_KV_PADDED) != 0;
-    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
-    if (v != 0 && v != 12) {
-        yume_set_error("attn_fwd_fband: variant %d has no frame-banded kernel (variants 0 and 12 do)", v);
-        return YUME_EUNSUP;
-    }
+    YUME_REQUIRE(Lk <= N, "%s: Lk=%lld keys exceed the partition's N=%lld", who, (long long)Lk, (long long)N);
+    return YUME_OK;
+}
+
+static AttnArgs band_args(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo, int64_t Lq,
+                          int64_t Lk, int64_t H, float scale, int accumulate, int q_pre) {
     AttnArgs a{};
     a.Q = (const unsigned short*)Q; a.ldq = ldq;
     a.K = (const unsigned short*)K; a.ldk = ldk;
@@ -377,6 +373,29 @@ extern "C" int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, in
     a.accumulate = accumulate;
     a.splits = 1;
     a.last_w = 1.0f;
+    return a;
+}
+
+// Frame-window / frame-causal attention (attn_fband.hpp): the key axis is partitioned into blocks by nspan uniform spans (host arrays, copied
+// into the kernel arguments); row i sits at q_pos0 + i and sees every key of the blocks within `back` before and `ahead` after its own
+// (attn_fband_plan::visible). A (partition, back, ahead, q_pos0) that hides no (row, key) pair of the call IS yume_attn_fwd_ws.
+extern "C" int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                                   int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant, int64_t q_pos0, int64_t nspan,
+                                   const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    attn_fband_plan::Plan w;
+    int64_t N, NB;
+    const int rc = fband_check("attn_fwd_fband", Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, q_pos0, nspan, span_rows, span_blocks, back, ahead, w, N, NB);
+    if (rc != YUME_OK) return rc;
+    if (attn_fband_plan::hides_nothing(Lq, Lk, w))
+        return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, stream);
+    const int q_pre = (variant & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (variant & YUME_ATTN_KV_PADDED) != 0;
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 12) {
+        yume_set_error("attn_fwd_fband: variant %d has no frame-banded kernel (variants 0 and 12 do)", v);
+        return YUME_EUNSUP;
+    }
+    const AttnArgs a = band_args(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, q_pre);
     if (attn_log_on()) {
         int64_t tmin = INT64_MAX, tmax = 0;
         for (int64_t q = 0; q < Lq; q += QB) {
@@ -392,6 +411,49 @@ extern "C" int yume_attn_fwd_fband(const void* Q, int64_t ldq, const void* K, in
     }
     attn_fband::launch(a, w, (hipStream_t)stream);
     YUME_CHECK_LAUNCH("attn_fwd_fband");
+    return YUME_OK;
+}
+
+// The frame window with an always-visible sink (attn_fsink.hpp): the first `sink` blocks of the partition are seen by every row
+// (attn_fsink_plan::visible). A call that hides nothing IS yume_attn_fwd_ws; a sink that shows nothing the window hides IS
+// yume_attn_fwd_fband; only a call whose sink adds a pair runs the kernel.
+extern "C" int yume_attn_fwd_fsink(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                                   int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant, int64_t q_pos0, int64_t nspan,
+                                   const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead, int64_t sink,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    attn_fband_plan::Plan w;
+    int64_t N, NB;
+    const int rc = fband_check("attn_fwd_fsink", Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, q_pos0, nspan, span_rows, span_blocks, back, ahead, w, N, NB);
+    if (rc != YUME_OK) return rc;
+    YUME_REQUIRE(sink >= 0 && sink <= NB, "attn_fwd_fsink: sink=%lld must be in [0, NB=%lld] (the leading blocks every row sees)", (long long)sink,
+                 (long long)NB);
+    if (attn_fsink_plan::hides_nothing(Lq, Lk, w, sink))
+        return yume_attn_fwd_ws(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, workspace, workspace_bytes, stream);
+    if (sink == 0 || attn_fsink_plan::adds_nothing(Lq, Lk, w, sink))
+        return yume_attn_fwd_fband(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, q_pos0, nspan, span_rows, span_blocks,
+                                   back, ahead, workspace, workspace_bytes, stream);
+    const int q_pre = (variant & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (variant & YUME_ATTN_KV_PADDED) != 0;
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 13) {
+        yume_set_error("attn_fwd_fsink: variant %d has no frame-sink kernel (variants 0 and 13 do)", v);
+        return YUME_EUNSUP;
+    }
+    const AttnArgs a = band_args(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, q_pre);
+    if (attn_log_on()) {
+        int64_t tmin = INT64_MAX, tmax = 0;
+        for (int64_t q = 0; q < Lq; q += QB) {
+            const int64_t n = attn_fsink_plan::tile_count(attn_fsink_plan::tile_list(q, (q + QB < Lq ? q + QB : Lq) - 1, Lk, w, sink));
+            tmin = n < tmin ? n : tmin;
+            tmax = n > tmax ? n : tmax;
+        }
+        fprintf(stderr, "[attn_fwd_fsink] fsink q_pos0=%lld back=%lld ahead=%lld sink=%lld sink_rows=%lld nspan=%lld nblocks=%lld tiles_min=%lld "
+                        "tiles_max=%lld Lq=%d Lk=%d H=%d ldq=%lld ldk=%lld ldvt=%lld ldo=%lld prescaled=%d kv_padded=%d accumulate=%d\n",
+                (long long)q_pos0, (long long)back, (long long)ahead, (long long)sink, (long long)attn_fsink_plan::send(Lk, w, sink), (long long)nspan,
+                (long long)NB, (long long)tmin, (long long)tmax, a.Lq, a.Lk, a.H, (long long)ldq, (long long)ldk, (long long)ldvt, (long long)ldo, q_pre,
+                kv_pad, accumulate);
+    }
+    attn_fsink::launch(a, w, sink, (hipStream_t)stream);
+    YUME_CHECK_LAUNCH("attn_fwd_fsink");
     return YUME_OK;
 }
 

@@ -134,6 +134,12 @@ class DiTEngine:
         fw = os.environ.get("YUME_FRAME_WINDOW", "").strip()
         self.frame_window = tuple(int(v) for v in fw.split(",")) if fw else None
         self._spans = None            # the current clip's (rows, blocks) spans, kept by _prologue while frame_window is set
+        # r29: the frame window's sink — the first frame_sink frames of the clip stay visible to every token whatever the window
+        # (yume_attn_fwd_fsink). Under FramePack frame 0 is the clip's first frame (framepack.history_groups puts it first): the conditioning
+        # image of the I2V models, which a local window hides from every frame more than `back` frames on. Needs a frame_window; counts above
+        # the clip's frames mean all of them. It reaches the kernel through _frame_args alone. 0 = r28's calls, bit for bit; env
+        # YUME_FRAME_SINK sets it.
+        self.frame_sink = int(os.environ.get("YUME_FRAME_SINK", "0").strip() or 0)
         # r27: a captured hipGraph holds raw pointers to what the engine handed it — the _buf workspaces, the per-clip tables, the packed
         # weights — and knows nothing of _ws, _plan_cache or P. What a capture was handed is kept here (workspaces once per storage), so a later
         # eager call at another shape, a flipped pack option or the emptying plan cache replaces the engine's entry but frees nothing a replay
@@ -521,7 +527,11 @@ class DiTEngine:
     def _frame_args(self, q_pos0, n_rows=None):
         """the frame-window arguments of a self-attention ops.attn_fwd call whose first query row is token q_pos0; none without a
         frame_window. n_rows: the call's query rows where they outnumber the clip's tokens (the sequence-parallel pad rows): the rows behind
-        the last token are one more block, seen by nobody (they lie behind Lk)."""
+        the last token are one more block, seen by nobody (they lie behind Lk). With a frame_sink, min(frame_sink, the clip's frames) of it."""
+        sink = int(self.frame_sink)
+        if sink != 0 and (sink < 0 or self.frame_window is None):
+            raise ValueError(f"DiTEngine.frame_sink={self.frame_sink} with frame_window={self.frame_window}: the sink is a non-negative count of "
+                             "leading frames beside a frame_window (set engine.frame_window, or engine.frame_sink = 0)")
         if self.frame_window is None:
             return {}
         if self._windowed():
@@ -536,9 +546,10 @@ class DiTEngine:
                                       "the model's forward, or set engine.frame_window = None)")
         spans = list(self._spans)
         n_tok = sum(r * b for r, b in spans)
+        extra = {"frame_sink": min(sink, sum(b for _, b in spans))} if sink else {}
         if n_rows is not None and n_rows > n_tok:
             spans.append((n_rows - n_tok, 1))
-        return {"frame_window": fw, "spans": spans, "q_pos0": int(q_pos0)}
+        return {"frame_window": fw, "spans": spans, "q_pos0": int(q_pos0), **extra}
 
     def _refuse_frame_window(self, who):
         if self.frame_window is not None:

@@ -586,7 +586,7 @@ ATTN_KV_PADDED = 0x200       # YUME_ATTN_KV_PADDED
 
 
 def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False,
-             last_key_weight=1.0, window=(-1, -1), q_pos0=0, frame_window=None, spans=None):
+             last_key_weight=1.0, window=(-1, -1), q_pos0=0, frame_window=None, spans=None, frame_sink=0):
     """out[Lq, H*128] = softmax(q k^T * scale) v ; q,k token-major bf16 2-D views, vt K-major [H*128, >=Lk].
     q_prescaled: q already carries scale * log2(e) (`scale` is ignored): out = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j).
     kv_padded: the caller guarantees that k's storage is readable up to ceil(Lk/64)*64 rows and that vt has that many columns with finite
@@ -599,9 +599,14 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     frame_window = (back, ahead), spans = [(rows, blocks), ...], q_pos0: the key axis is partitioned into blocks (frames) by the spans in order,
     `blocks` blocks of `rows` rows each; query row i sits at q_pos0 + i and sees every key of the blocks within `back` before and `ahead` after
     its own (-1: unbounded on that side; (-1, 0) is frame-causal; yume_attn_fwd_fband, variants 0 and 12, no weighted last key, no token
-    window beside it). None (the default): the call is the one it always was."""
+    window beside it). None (the default): the call is the one it always was.
+    frame_sink = n > 0, with a frame_window: the first n blocks of the partition are seen by every row as well (0 <= n <= the partition's
+    blocks; yume_attn_fwd_fsink, variants 0 and 13). 0 (the default): the call is the one it always was."""
     lib = _lib.load()
     window = (int(window[0]), int(window[1]))
+    frame_sink = int(frame_sink)
+    if frame_sink != 0 and frame_window is None:
+        raise RuntimeError(f"yume_amd.attn_fwd: frame_sink={frame_sink} needs a frame_window (the sink is the frame window's: yume_attn_fwd_fsink)")
     if frame_window is not None:
         if window != (-1, -1):
             raise RuntimeError("yume_amd.attn_fwd: frame_window and window do not combine (one mask per call)")
@@ -653,6 +658,12 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     if frame_window is not None:
         import ctypes
         arr = ctypes.c_int64 * max(len(spans), 1)          # host arrays: read during the call, handed to the kernel by value
+        if frame_sink != 0:
+            rc = lib.yume_attn_fwd_fsink(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), len(spans),
+                                         arr(*[r for r, _ in spans]), arr(*[b for _, b in spans]), int(frame_window[0]), int(frame_window[1]),
+                                         frame_sink, _ptr(ws), nbytes if ws is not None else 0, _stream())
+            _lib.check(rc, "yume_attn_fwd_fsink")
+            return out
         rc = lib.yume_attn_fwd_fband(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), len(spans),
                                      arr(*[r for r, _ in spans]), arr(*[b for _, b in spans]), int(frame_window[0]), int(frame_window[1]),
                                      _ptr(ws), nbytes if ws is not None else 0, _stream())
