@@ -453,6 +453,30 @@ int yume_attn_fwd_fsink(const void* Q, int64_t ldq, const void* K, int64_t ldk, 
                         void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
                         int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead,
                         int64_t sink, void* workspace, int64_t workspace_bytes, void* stream);
+/* FRAME-WINDOW form OVER TWO KEY BUFFERS (r30; a function added, no argument list changed: ABI 9). yume_attn_fwd_fband's arguments describe
+ * the SUFFIX (K / Vt / Lk / the spans / back / ahead / q_pos0, with its own key numbering from 0); Kp [n_prefix, H*128] rows ldkp apart and
+ * Vtp [H*128, >= n_prefix] rows ldvtp apart are a PREFIX of n_prefix keys in a buffer of their own:
+ *   visible(i, j_prefix) for every 0 <= j_prefix < n_prefix;   visible(i, j_suffix)  <=>  yume_attn_fwd_fband's rule on the suffix arguments
+ *   O[h,i,:] = exact softmax over the union, in the logical order prefix then suffix. With n_prefix >= 1 no row is empty.
+ * replaces: nothing the reference computes. It is what lets a frame-causal FramePack forward keep the K rows / V^T columns of its history
+ *           tokens from one denoise step to the next (DiTEngine.cache_history): the history keys are the prefix, the frames being denoised the
+ *           suffix, and neither buffer is padded or copied behind the other (n_hist is no multiple of 8, V^T images start 16-byte aligned).
+ * Checks (YUME_EINVAL by name `attn_fwd_fprefix`): everything yume_attn_fwd_fband checks on the suffix; n_prefix >= 0; n_prefix + N < 2^31;
+ *    with n_prefix > 0: Kp / Vtp non-NULL and 16-byte aligned, ldkp % 8 == 0, ldvtp % 8 == 0, ldvtp >= n_prefix.
+ * Normalisation: n_prefix == 0 IS yume_attn_fwd_fband with the same suffix arguments (same log line, same bits, its variants). Every
+ *    n_prefix >= 1 runs the kernel (attn_fprefix.hpp: the ceil(n_prefix / 64) prefix tiles, then the suffix's band tiles, the prefetch
+ *    switching buffers and strides in between; a ragged last tile of either segment is register-staged with that segment's key bound, so
+ *    neither buffer needs padding and no key behind n_prefix or Lk enters a product): variant 0 and variant 14 = that kernel; any other
+ *    variant: YUME_EUNSUP (the message names it).
+ * accumulate, ragged Lq and both scale modes as for yume_attn_fwd_fband; YUME_ATTN_KV_PADDED is accepted and changes nothing. No key weight, no
+ *    key-range split; the workspace is handed on to yume_attn_fwd_fband and otherwise unused.
+ * env YUME_ATTN_LOG=1: one line per call that runs the kernel, `[attn_fwd_fprefix] fprefix n_prefix=.. prefix_tiles=.. q_pos0=.. back=..
+ *    ahead=.. nspan=.. nblocks=.. tiles_min=.. tiles_max=.. Lq=.. Lk=.. H=.. ...`. tests/test_attn_fprefix_routes_gpu.py reads it. */
+int yume_attn_fwd_fprefix(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt,
+                          void* O, int64_t ldo, int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant,
+                          int64_t q_pos0, int64_t nspan, const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead,
+                          const void* Kp, int64_t ldkp, const void* Vtp, int64_t ldvtp, int64_t n_prefix,
+                          void* workspace, int64_t workspace_bytes, void* stream);
 /* SEGMENTED form (r9): ONE launch serves nseg (1 .. 8) independent attention problems that share Q's and O's buffers and every shape but the
  * key count. Segment s owns the query rows [s * seg_pitch, s * seg_pitch + Lq_seg) of Q and O (seg_pitch >= Lq_seg, in rows; the rows of the
  * gap are neither read nor written) and attends over its own K[s] / Vt[s] (Lk[s] keys, key Lk[s] - 1 counting last_key_weight[s] times).

@@ -52,6 +52,7 @@ SIGNATURES = {
     "yume_attn_fwd_band": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _L, _L, _L, _P, _L, _P],
     "yume_attn_fwd_fband": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _L, _L, _P, _P, _L, _L, _P, _L, _P],
     "yume_attn_fwd_fsink": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _L, _L, _P, _P, _L, _L, _L, _P, _L, _P],
+    "yume_attn_fwd_fprefix": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _F, _I, _I, _L, _L, _P, _P, _L, _L, _P, _L, _P, _L, _L, _P, _L, _P],
     "yume_attn_fwd_seg": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _F, _I, _I, _P, _P],
     "yume_attn_batch_workspace_bytes": [_L, _L, _L, _L],
     "yume_attn_fwd_batch": [_P, _L, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _L, _L, _F, _I, _I, _P, _L, _P],

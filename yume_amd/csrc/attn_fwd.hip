@@ -18,7 +18,8 @@
 // yume_attn_fwd_band (sliding-window / causal attention) has the banded form of attn_fwd_kernel_v2: attn_band.hpp, planned by attn_band_plan.hpp.
 // yume_attn_fwd_fband (frame-window / frame-causal attention over a block partition) has that walk with another interval source: attn_fband.hpp,
 // planned by attn_fband_plan.hpp. yume_attn_fwd_fsink adds an always-visible sink of leading blocks: a walk over a tile LIST, attn_fsink.hpp,
-// planned by attn_fsink_plan.hpp.
+// planned by attn_fsink_plan.hpp. yume_attn_fwd_fprefix is the frame window over two key buffers, an always-visible prefix in a buffer of
+// its own and the suffix under the window: attn_fprefix.hpp, planned by attn_fprefix_plan.hpp.
 // and attn_combine_kernel (attn_combine.hpp) merges the key-range pieces of a split v7 / v8 launch, planned by attn_plan.hpp.
 // The transposed formulation and the tile layouts the kernels share: attn_tile.hpp.
 #include "common.hpp"
@@ -35,6 +36,7 @@
 #include "attn_band.hpp"
 #include "attn_fband.hpp"
 #include "attn_fsink.hpp"
+#include "attn_fprefix.hpp"
 #include <math.h>
 
 static_assert(attn_plan::QBLOCK == QB4 && attn_plan::KTILE == KT && attn_plan::HDIM == D, "attn_plan.hpp restates the tile constants");
@@ -454,6 +456,54 @@ extern "C" int yume_attn_fwd_fsink(const void* Q, int64_t ldq, const void* K, in
     }
     attn_fsink::launch(a, w, sink, (hipStream_t)stream);
     YUME_CHECK_LAUNCH("attn_fwd_fsink");
+    return YUME_OK;
+}
+
+// The frame window over two key buffers (attn_fprefix.hpp): every row sees the n_prefix keys of Kp / Vtp, and the keys of K / Vt that
+// yume_attn_fwd_fband's rule shows it (K / Vt / Lk / the spans / back / ahead / q_pos0 describe that suffix, numbered from 0). n_prefix == 0 IS
+// yume_attn_fwd_fband with the suffix arguments; every n_prefix >= 1 runs the kernel (there is no one-buffer call to forward to).
+extern "C" int yume_attn_fwd_fprefix(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, int64_t ldvt, void* O, int64_t ldo,
+                                     int64_t Lq, int64_t Lk, int64_t H, float scale, int accumulate, int variant, int64_t q_pos0, int64_t nspan,
+                                     const int64_t* span_rows, const int64_t* span_blocks, int64_t back, int64_t ahead, const void* Kp,
+                                     int64_t ldkp, const void* Vtp, int64_t ldvtp, int64_t n_prefix, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+    attn_fband_plan::Plan w;
+    int64_t N, NB;
+    const int rc = fband_check("attn_fwd_fprefix", Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, q_pos0, nspan, span_rows, span_blocks, back, ahead, w, N, NB);
+    if (rc != YUME_OK) return rc;
+    YUME_REQUIRE(n_prefix >= 0, "attn_fwd_fprefix: n_prefix=%lld must be >= 0", (long long)n_prefix);
+    YUME_REQUIRE(n_prefix < (1ll << 31) && n_prefix + N < (1ll << 31), "attn_fwd_fprefix: n_prefix=%lld + the partition's N=%lld must be below 2^31",
+                 (long long)n_prefix, (long long)N);
+    if (n_prefix == 0)
+        return yume_attn_fwd_fband(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, variant, q_pos0, nspan, span_rows, span_blocks,
+                                   back, ahead, workspace, workspace_bytes, stream);
+    YUME_REQUIRE(Kp && Vtp, "attn_fwd_fprefix: NULL pointer (Kp / Vtp with n_prefix=%lld)", (long long)n_prefix);
+    YUME_REQUIRE((ldkp % 8) == 0 && (ldvtp % 8) == 0, "attn_fwd_fprefix: ldkp / ldvtp must be multiples of 8");
+    YUME_REQUIRE(ldkp < (1ll << 24) && ldvtp < (1ll << 24), "attn_fwd_fprefix: ldkp / ldvtp too large for 32-bit tile offsets");
+    YUME_REQUIRE(ldvtp >= n_prefix && ldvtp >= 8, "attn_fwd_fprefix: ldvtp=%lld must be >= n_prefix=%lld", (long long)ldvtp, (long long)n_prefix);
+    YUME_REQUIRE(((uintptr_t)Kp % 16) == 0 && ((uintptr_t)Vtp % 16) == 0, "attn_fwd_fprefix: pointer alignment (Kp / Vtp)");
+    const int q_pre = (variant & YUME_ATTN_Q_PRESCALED) != 0, kv_pad = (variant & YUME_ATTN_KV_PADDED) != 0;
+    const int v = variant & ~(YUME_ATTN_Q_PRESCALED | YUME_ATTN_KV_PADDED);
+    if (v != 0 && v != 14) {
+        yume_set_error("attn_fwd_fprefix: variant %d has no frame-prefix kernel (variants 0 and 14 do)", v);
+        return YUME_EUNSUP;
+    }
+    const AttnArgs a = band_args(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Lq, Lk, H, scale, accumulate, q_pre);
+    if (attn_log_on()) {
+        int64_t tmin = INT64_MAX, tmax = 0;
+        for (int64_t q = 0; q < Lq; q += QB) {
+            const int64_t n = attn_fsink_plan::tile_count(attn_fprefix_plan::tile_list(q, (q + QB < Lq ? q + QB : Lq) - 1, Lk, w, n_prefix));
+            tmin = n < tmin ? n : tmin;
+            tmax = n > tmax ? n : tmax;
+        }
+        fprintf(stderr, "[attn_fwd_fprefix] fprefix n_prefix=%lld prefix_tiles=%lld q_pos0=%lld back=%lld ahead=%lld nspan=%lld nblocks=%lld "
+                        "tiles_min=%lld tiles_max=%lld Lq=%d Lk=%d H=%d ldq=%lld ldk=%lld ldvt=%lld ldkp=%lld ldvtp=%lld ldo=%lld prescaled=%d "
+                        "kv_padded=%d accumulate=%d\n", (long long)n_prefix, (long long)attn_fprefix_plan::prefix_tiles(n_prefix), (long long)q_pos0,
+                (long long)back, (long long)ahead, (long long)nspan, (long long)NB, (long long)tmin, (long long)tmax, a.Lq, a.Lk, a.H, (long long)ldq,
+                (long long)ldk, (long long)ldvt, (long long)ldkp, (long long)ldvtp, (long long)ldo, q_pre, kv_pad, accumulate);
+    }
+    attn_fprefix::launch(a, w, Kp, ldkp, Vtp, ldvtp, n_prefix, (hipStream_t)stream);
+    YUME_CHECK_LAUNCH("attn_fwd_fprefix");
     return YUME_OK;
 }
 

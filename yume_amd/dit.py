@@ -140,6 +140,23 @@ class DiTEngine:
         # the clip's frames mean all of them. It reaches the kernel through _frame_args alone. 0 = r28's calls, bit for bit; env
         # YUME_FRAME_SINK sets it.
         self.frame_sink = int(os.environ.get("YUME_FRAME_SINK", "0").strip() or 0)
+        # r30: under the frame-causal mask (frame_window = (-1, 0)) no history token of a FramePack sequence sees a token of the frames being
+        # denoised; the 5B family gives the history rows the timestep t[0] and keeps their latents clean, and cross-attention and the FFN are
+        # row-local: every history row of the residual stream, hence its K row and V^T column in every block, is the same at every denoise
+        # step of a chunk. With cache_history the first qualifying forward_one after reset_history() (or after a change of the cache key:
+        # clip shape, conditioning, pack, dedup_pad_keys) is a RECORD forward — today's forward, bit for bit, that also copies each block's
+        # history K rows / V^T columns into engine-owned buffers — and every later one a REPLAY: the new frames' rows only, their
+        # self-attention over the cached keys as an always-visible prefix (yume_attn_fwd_fprefix). The caller promises that the history
+        # frames of u and t[0] are the recorded ones (sampling.make_velocity_5b's loop does; history_check compares them, with a sync).
+        # Needs family wan23, the packed path, frame_window == (-1, 0), no window_size, no sequence parallelism, no block-residual cache.
+        # Off by default = today's path, bit for bit; env YUME_CACHE_HISTORY=1 turns it on.
+        self.cache_history = os.environ.get("YUME_CACHE_HISTORY", "0") == "1"
+        self.history_check = os.environ.get("YUME_HISTORY_CHECK", "0") == "1"
+        self._hist_key = None         # the cache key of the recorded history; None: the next qualifying forward records
+        self._hist_refs = None        # the conditioning tensors of the key (their addresses stay theirs while the entry is live)
+        self._hist_rec = None         # n_hist while a record forward is under way: _blocks / _trimmed_block copy K / V^T behind rmsnorm_rope
+        self._hist_kept = None        # history_check: (the history frames of u, t[0]) at record time
+        self._hist_said = False
         # r27: a captured hipGraph holds raw pointers to what the engine handed it — the _buf workspaces, the per-clip tables, the packed
         # weights — and knows nothing of _ws, _plan_cache or P. What a capture was handed is kept here (workspaces once per storage), so a later
         # eager call at another shape, a flipped pack option or the emptying plan cache replaces the engine's entry but frees nothing a replay
@@ -427,7 +444,7 @@ class DiTEngine:
         return kc, vct
 
     def _blocks(self, xs, L, tab, row_idx, R, rope, n_rope, ctx, n_img, ctx_fresh=True, n_keys=None, only=None, cache=None, n_trim=0,
-                txt_last_weight=1.0):
+                txt_last_weight=1.0, hist=0):
         """xs fp32 [L, C] in/out. tab fp32 [nb, R, 6, C]; rope fp32 [n_rope, 64, 2] (n_rope == L here).
         txt_last_weight: how many keys the LAST text row of ctx stands for (dedup_pad_keys: text_len - n; 1 = every row is one key).
         n_trim: the first n_trim rows of the LAST block's output are not needed by the caller (history tokens in front of the head): that
@@ -435,16 +452,20 @@ class DiTEngine:
         With sequence parallelism L is this rank's (padded) chunk and n_keys the true global token count.
         only: run just these block indices (tab[j] then belongs to only[j]) — the WanAttentionBlock.forward seam.
         cache: (mode, cache_list, tensors) block-residual cache of wan/modules/model.py:985-1000: mode 'record' appends
-        bf16 (x_out - x_in) of the listed blocks, 'replay' adds the stored residual instead of running them."""
+        bf16 (x_out - x_in) of the listed blocks, 'replay' adds the stored residual instead of running them.
+        hist = n_hist > 0: a cache_history REPLAY. xs, row_idx and rope are the L = n_new_tok rows of the frames being denoised alone (row 0
+        of every buffer is the first new token), in workspaces of the replay's own (`*_hr`: a longer eager forward never leaves its rows in
+        their padding), and the self-attention runs over the recorded history keys as a prefix (_self_attn_history)."""
         m = self.model
         C, H, Fd, eps = m.dim, m.num_heads, m.ffn_dim, m.eps
         # q|k rows and V^T columns exist (zeros) up to a whole number of 64-key tiles: YUME_ATTN_KV_PADDED (see _cross_kv)
         Lp = _round_up(L, 64)
-        h = self._buf("h", (L, C), torch.bfloat16)
-        qk = self._buf("qk", (Lp, 2 * C), torch.bfloat16, zero=True)[:L]
-        vt = self._buf("vt", (C, Lp), torch.bfloat16, zero=True)
-        att = self._buf("att", (L, C), torch.bfloat16)
-        ff = self._buf("ff", (L, Fd), torch.bfloat16)
+        sfx = "_hr" if hist else ""
+        h = self._buf("h" + sfx, (L, C), torch.bfloat16)
+        qk = self._buf("qk" + sfx, (Lp, 2 * C), torch.bfloat16, zero=True)[:L]
+        vt = self._buf("vt" + sfx, (C, Lp), torch.bfloat16, zero=True)
+        att = self._buf("att" + sfx, (L, C), torch.bfloat16)
+        ff = self._buf("ff" + sfx, (L, Fd), torch.bfloat16)
         ts = 6 * C  # table row stride
         ntxt = ctx.shape[0] - n_img
         kc_t, vct_t = self._cross_kv("t", ctx[n_img:], ntxt, self.P["wkv_c"], self.P["bkv_c"], self.P["nk_c"], ctx_fresh)
@@ -479,7 +500,11 @@ class DiTEngine:
             else:
                 ops.rmsnorm_rope(qk[:n_rope], C, 2, d["nqk"], self.qk_eps, rope)
                 ops.rmsnorm_rope(qk[n_rope:], C, 2, d["nqk"], self.qk_eps, None)
-            if self.sp is None:
+            if self._hist_rec:
+                self._hist_record(i, qk, vt)
+            if hist:
+                sa = self._self_attn_history(i, qk, vt, att, L, hist)
+            elif self.sp is None:
                 sa = self._self_attn_step(qk, vt, att, 0, L, n_keys if n_keys is not None else L)
             else:      # Ulysses: all tokens x this rank's heads, then back (2 collectives, yume_amd/ulysses.py)
                 self._fp8_attn_notice("the sequence-parallel self-attention keeps the bf16 kernels")
@@ -592,6 +617,75 @@ class DiTEngine:
         T("attn_self", ops.attn_fwd, qk[s:, :C], qk[:, C:], vt, out, L - s, n_keys, H, variant=self.attn_variant, q_prescaled=self.q_prescale,
           kv_padded=True, **self._window_args(s), **self._frame_args(s))
         return out
+
+    # ------------------------------------------------------------------ the frame-causal history cache (r30)
+    def reset_history(self):
+        """forget the recorded history: the next qualifying forward_one records again (sampling.make_velocity_5b calls it once per chunk)"""
+        self._hist_key = self._hist_refs = self._hist_kept = None
+
+    def _hist_bufs(self, i, n_hist):
+        """block i's cache: Kc [n_hist, C] and Vc [C, ceil8(n_hist)] (engine-owned workspaces: a capture that is handed them pins them)"""
+        C = self.model.dim
+        return (self._buf(f"hist_k{i}", (n_hist, C), torch.bfloat16),
+                self._buf(f"hist_vt{i}", (C, _round_up(n_hist, 8)), torch.bfloat16, zero=True))
+
+    def _hist_record(self, i, qk, vt):
+        """behind block i's rmsnorm_rope of a record forward: the history tokens' K rows and V^T columns, as every later step will need them"""
+        n, C = self._hist_rec, self.model.dim
+        kc, vc = self._hist_bufs(i, n)
+        kc.copy_(qk[:n, C:])
+        vc[:, :n].copy_(vt[:, :n])
+
+    def _self_attn_history(self, i, qk, vt, out, L, n_hist):
+        """the self-attention of block i of a replay: the L new rows over the n_hist recorded keys (seen by every row) and their own keys
+        under the frame-causal rule on the new group's span — yume_attn_fwd_fprefix. fp8_attn keeps this bf16 kernel."""
+        C, H = self.model.dim, self.model.num_heads
+        self._fp8_attn_notice("self-attention stays bf16: a cache_history replay runs the bf16 frame-prefix kernel")
+        kc, vc = self._hist_bufs(i, n_hist)
+        self._timed("attn_self", ops.attn_fwd, qk[:, :C], qk[:, C:], vt, out, L, L, H, variant=self.attn_variant, q_prescaled=self.q_prescale,
+                    frame_window=(-1, 0), spans=[self._spans[-1]], q_pos0=0, prefix=(kc, vc, n_hist))
+        return out
+
+    def _history_mode(self, u, t, context, clip_fea, packed, lfz, n_sel, cache):
+        """None with cache_history off; otherwise the preconditions (each refusal names the option and what it met), then ("record" | "replay",
+        the cache key)"""
+        if not self.cache_history:
+            return None
+        who = "DiTEngine.cache_history"
+        if self.family != "wan23":
+            raise NotImplementedError(f"{who} needs the wan23 (5B) family: the {self.family!r} family has one scalar t and re-noises its history "
+                                      "every step, so its history rows are not step-invariant (set engine.cache_history = False)")
+        if not packed or t.numel() < 2:
+            raise ValueError(f"{who} needs the packed (FramePack) path with a per-token t (t[0] history, t[-1] new), got packed={packed} and "
+                             f"{t.numel()} timestep(s)")
+        fw = None if self.frame_window is None else tuple(int(v) for v in self.frame_window)
+        if fw != (-1, 0):
+            raise ValueError(f"{who} needs frame_window == (-1, 0) (frame-causal: no history token sees a new frame), got frame_window={fw}")
+        if self._windowed():
+            raise ValueError(f"{who} and window_size={tuple(self.window_size)} do not combine (needs window_size == (-1, -1))")
+        if self.sp is not None:
+            raise NotImplementedError(f"{who} is not combined with sequence parallelism (engine.sp must be None)")
+        if cache is not None:
+            raise NotImplementedError(f"{who} is not combined with the block-residual cache (forward_one's cache argument must be None)")
+        Cin, F, H, W = u.shape
+        key = (("p", F, H, W, lfz, n_sel),
+               (context.data_ptr(), context._version, tuple(context.shape),
+                None if clip_fea is None else (clip_fea.data_ptr(), clip_fea._version, tuple(clip_fea.shape)), self._packed_key,
+                self.dedup_pad_keys), self._packed_key, self.dedup_pad_keys)
+        if key == self._hist_key and not (self.history_check and self._hist_kept is None):      # (a check switched on later: record again)
+            if self.history_check:
+                hu, ht = self._hist_kept
+                if not torch.equal(u[:, :F - lfz].to(hu.device, hu.dtype), hu):
+                    raise RuntimeError(f"{who}: the history frames of u differ from the recorded ones (history_check; call "
+                                       "engine.reset_history() when the history changes)")
+                if float(t.reshape(-1)[0]) != ht:
+                    raise RuntimeError(f"{who}: t[0]={float(t.reshape(-1)[0])} differs from the recorded {ht} (history_check; call "
+                                       "engine.reset_history() when the history's timestep changes)")
+            return "replay", key
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: the record forward cannot run under a stream capture (run one eager forward of this clip, "
+                               "conditioning and pack first; a replay captures)")
+        return "record", key
 
     def _qkv_step(self, d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps):
         """the first adaLN of a block and its QKV projection, behind _blocks, _trimmed_block, _blocks_pair and _blocks_batch alike: q | k into
@@ -715,6 +809,8 @@ class DiTEngine:
         n = L - s
         self._qkv_step(d, xs, scale_sa, shift_sa, ts, row_idx, h, qk, vt, eps)
         T("rmsnorm_rope", ops.rmsnorm_rope, qk, C, 2, d["nqk"], self.qk_eps, rope)
+        if self._hist_rec:
+            self._hist_record(i, qk, vt)
         self._self_attn_step(qk, vt, ao, s, L, L)
         T("gemm_o", ops.gemm_bf16, ao, d["wo"], d["bo"], xo, EPI_RESID, gate=gate_sa, gate_stride=ts, row_idx=ro, variant=self.gemm_variant)
         self._cross_q_step(d, xo, ho, qo, eps)
@@ -784,11 +880,12 @@ class DiTEngine:
         return y
 
     # ------------------------------------------------------------------ one sample forward
-    def _prologue(self, u, t, packed, lfz, n_sel, pair=False, xs_rows=None):
+    def _prologue(self, u, t, packed, lfz, n_sel, pair=False, xs_rows=None, new_only=False):
         """what a forward does before the conditioning enters: the per-clip tables, the timestep rows, the patch embedding into the residual
         stream and the modulation table. Returns (xs, L, n_hist, grid, rope, R, row_idx, e, tab). pair: the residual stream is forward_pair's
         stacked buffer (the embedding fills its first L rows). xs_rows: a function L -> the rows of the residual stream the embedding fills
-        (forward_batch: one sample's rows of its stacked buffer)."""
+        (forward_batch: one sample's rows of its stacked buffer). new_only (a cache_history replay, packed): only the group of the frames being
+        denoised is embedded, into a residual stream of n_new_tok rows; everything else returned is the whole clip's."""
         m = self.model
         C, D = m.dim, m.dim // m.num_heads
         if D != 128:
@@ -852,7 +949,10 @@ class DiTEngine:
             row_idx = inv.to(torch.int32).contiguous()
 
         # --- embeddings
-        if xs_rows is not None:
+        if new_only:
+            groups = groups[-1:]
+            xs = self._buf("xs_hr", (groups[0].ntok, C), torch.float32)
+        elif xs_rows is not None:
             xs = xs_rows(L)
         else:
             xs = self._buf("xs_p", (_round_up(L, 64) + L, C), torch.float32) if pair else self._buf("xs", (L, C), torch.float32)
@@ -873,7 +973,9 @@ class DiTEngine:
         self.ensure_packed()
         m = self.model
         C = m.dim
-        xs, L, n_hist, grid, rope, R, row_idx, e, tab = self._prologue(u, t, packed, lfz, n_sel)
+        hist = self._history_mode(u, t, context, clip_fea, packed, lfz, n_sel, cache)
+        replay = hist is not None and hist[0] == "replay"
+        xs, L, n_hist, grid, rope, R, row_idx, e, tab = self._prologue(u, t, packed, lfz, n_sel, new_only=replay)
         nb = len(self.P["blocks"])
         n_img = 0
         if self.family == "wan":
@@ -905,8 +1007,24 @@ class DiTEngine:
             if cache is not None:
                 raise NotImplementedError("cache_sample is not combined with sequence parallelism")
             return self._forward_sp(xs, L, n_hist, tab.view(nb, R, 6, C), row_idx, R, rope, ctx, n_img, ctx_fresh, e, grid, txt_w)
+        if replay:
+            # the new rows alone, from row 0 of buffers of their own; nothing is left for trim_last_block to trim
+            Ln, ridx_new = L - n_hist, row_idx[n_hist:]
+            self._blocks(xs, Ln, tab.view(nb, R, 6, C), ridx_new, R, rope[n_hist:], Ln, ctx, n_img, ctx_fresh, txt_last_weight=txt_w, hist=n_hist)
+            return self._head(xs, ridx_new, e, R, grid)
         n_trim = n_hist if (self.trim_last_block and cache is None) else 0
-        self._blocks(xs, L, tab.view(nb, R, 6, C), row_idx, R, rope, L, ctx, n_img, ctx_fresh, cache=cache, n_trim=n_trim, txt_last_weight=txt_w)
+        if hist is not None:
+            # a record forward: today's forward, and each block's history K rows / V^T columns kept behind its rmsnorm_rope
+            self._hist_key = None
+            self._hist_rec = n_hist
+            self._hist_kept = (u[:, :u.shape[1] - lfz].detach().clone(), float(t.reshape(-1)[0])) if self.history_check else None
+        try:
+            self._blocks(xs, L, tab.view(nb, R, 6, C), row_idx, R, rope, L, ctx, n_img, ctx_fresh, cache=cache, n_trim=n_trim,
+                         txt_last_weight=txt_w)
+        finally:
+            self._hist_rec = None
+        if hist is not None:
+            self._hist_key, self._hist_refs = hist[1], (context, clip_fea)
         ridx_new = row_idx[n_hist:] if row_idx is not None else None
         return self._head(xs[n_hist:], ridx_new, e, R, grid)
 

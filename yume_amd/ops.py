@@ -586,7 +586,7 @@ ATTN_KV_PADDED = 0x200       # YUME_ATTN_KV_PADDED
 
 
 def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, use_workspace=True, q_prescaled=False, kv_padded=False,
-             last_key_weight=1.0, window=(-1, -1), q_pos0=0, frame_window=None, spans=None, frame_sink=0):
+             last_key_weight=1.0, window=(-1, -1), q_pos0=0, frame_window=None, spans=None, frame_sink=0, prefix=None):
     """out[Lq, H*128] = softmax(q k^T * scale) v ; q,k token-major bf16 2-D views, vt K-major [H*128, >=Lk].
     q_prescaled: q already carries scale * log2(e) (`scale` is ignored): out = sum_j 2^(q.k_j) v_j / sum_j 2^(q.k_j).
     kv_padded: the caller guarantees that k's storage is readable up to ceil(Lk/64)*64 rows and that vt has that many columns with finite
@@ -601,10 +601,21 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     its own (-1: unbounded on that side; (-1, 0) is frame-causal; yume_attn_fwd_fband, variants 0 and 12, no weighted last key, no token
     window beside it). None (the default): the call is the one it always was.
     frame_sink = n > 0, with a frame_window: the first n blocks of the partition are seen by every row as well (0 <= n <= the partition's
-    blocks; yume_attn_fwd_fsink, variants 0 and 13). 0 (the default): the call is the one it always was."""
+    blocks; yume_attn_fwd_fsink, variants 0 and 13). 0 (the default): the call is the one it always was.
+    prefix = (kp, vtp, n_prefix), with a frame_window: n_prefix more keys that every row sees, in buffers of their own (kp token-major
+    [>= n_prefix, H*128], vtp K-major [H*128, >= n_prefix]), in front of k / vt in the softmax's order; k, vt, Lk, spans, frame_window and
+    q_pos0 then describe the suffix alone, numbered from 0 (yume_attn_fwd_fprefix, variants 0 and 14, no frame_sink beside it). None (the
+    default): the call is the one it always was."""
     lib = _lib.load()
     window = (int(window[0]), int(window[1]))
     frame_sink = int(frame_sink)
+    if prefix is not None:
+        if frame_window is None:
+            raise ValueError("yume_amd.attn_fwd: prefix= needs a frame_window= (the prefix is the frame window's: yume_attn_fwd_fprefix)")
+        if frame_sink != 0:
+            raise ValueError(f"yume_amd.attn_fwd: prefix= and frame_sink={frame_sink} do not combine (the prefix is the always-visible part)")
+        pk, pvt, n_prefix = prefix
+        n_prefix = int(n_prefix)
     if frame_sink != 0 and frame_window is None:
         raise RuntimeError(f"yume_amd.attn_fwd: frame_sink={frame_sink} needs a frame_window (the sink is the frame window's: yume_attn_fwd_fsink)")
     if frame_window is not None:
@@ -658,6 +669,21 @@ def attn_fwd(q, k, vt, out, Lq, Lk, H, scale=None, accumulate=False, variant=0, 
     if frame_window is not None:
         import ctypes
         arr = ctypes.c_int64 * max(len(spans), 1)          # host arrays: read during the call, handed to the kernel by value
+        if prefix is not None:
+            pkp, ldkp, pvp, ldvp = None, 0, None, 0
+            if n_prefix > 0:
+                _dev(pk, "prefix k", torch.bfloat16)
+                _dev(pvt, "prefix vt", torch.bfloat16)
+                if pk.shape[0] < n_prefix or pk.shape[1] < H * 128 or pvt.shape[0] < H * 128 or pvt.shape[1] < n_prefix:
+                    raise RuntimeError(f"yume_amd.attn_fwd: prefix k {tuple(pk.shape)} / vt {tuple(pvt.shape)} do not hold {n_prefix} keys of "
+                                       f"{H} heads")
+                (pkp, ldkp), (pvp, ldvp) = _rows(pk, "prefix k"), _rows(pvt, "prefix vt")
+            rc = lib.yume_attn_fwd_fprefix(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0),
+                                           len(spans), arr(*[r for r, _ in spans]), arr(*[b for _, b in spans]), int(frame_window[0]),
+                                           int(frame_window[1]), pkp, ldkp, pvp, ldvp, n_prefix, _ptr(ws), nbytes if ws is not None else 0,
+                                           _stream())
+            _lib.check(rc, "yume_attn_fwd_fprefix")
+            return out
         if frame_sink != 0:
             rc = lib.yume_attn_fwd_fsink(qp, ldq, kp, ldk, vp, ldv, op, ldo, Lq, Lk, H, scale, 1 if accumulate else 0, flags, int(q_pos0), len(spans),
                                          arr(*[r for r, _ in spans]), arr(*[b for _, b in spans]), int(frame_window[0]), int(frame_window[1]),

@@ -25,6 +25,10 @@ def make_velocity_5b(model, context, seq_len, n_hist_tok, n_new_tok, sigmas, lfz
     dev = next(model.parameters()).device
     zeros = torch.zeros(n_hist_tok, dtype=torch.float64, device=dev)
     ones = torch.ones(n_new_tok, dtype=torch.float64, device=dev)
+    # one velocity per chunk: a history recorded for the previous chunk (DiTEngine.cache_history) ends here
+    reset = getattr(getattr(model, "engine", None), "reset_history", None)
+    if reset is not None:
+        reset()
 
     def velocity(latent, i):
         t = torch.cat([zeros, ones * (sigmas[i] * 1000.0)]).unsqueeze(0)
